@@ -18,6 +18,14 @@ configs[3] (b1 with RecurrentBackboneEncoder(MLP[256,256], LSTM(256)),
 8192 envs, self-play split, placed over the ranks: one policy per GPU at 8
 GPUs, all 8 on one GPU at N = 1).
 
+A plain run (``--gpus 1 --steps K --warmup W``) sets up, warms up, times
+the K updates and prints the result line.  ``--full`` adds the measurements
+that take runs of their own: the kernel rooflines (``roofline``,
+``kernels``), the headline with the sim step as its own launch
+(``separate_sim_ms_per_update``) and the CPU baseline (``cpu_baseline``);
+the ``--no-*`` options drop single legs of it.  ``--dump-outputs DIR``
+writes what the last timed update left with its caller (dump_outputs).
+
 Prints ONE JSON line on rank 0.
 """
 
@@ -99,6 +107,37 @@ def make(dev, total_envs, env_offset, n_local, dtype=torch.bfloat16, use_graph=T
         mgr = ml.init_training(dev, cfg, env.sim_fns(fused=fused_sim), policy,
                                use_graph=use_graph)
     return mgr
+
+
+DUMP_BUDGET_BYTES = 56 << 20  # of the 64 MB --dump-outputs may write
+
+
+def dump_outputs(mgr, out_dir):
+    """What the last update_iter left with its caller, as <out_dir>/<name>.npy
+    (float32): the flat parameters of every local policy, the rollout store
+    (values, rewards, dones, advantages, bootstrap values, actions and their
+    log-probabilities) and the update's metric records [policy, name, 5].
+    An array larger than its share of DUMP_BUDGET_BYTES is written as a
+    fixed sample: the elements at sorted flat indices drawn without
+    replacement by numpy's default_rng(0)."""
+    torch.cuda.synchronize()
+    s = mgr.rollout_mgr.store
+    m = mgr.metrics
+    arrays = {
+        "params": torch.cat([ps.params.reshape(-1) for ps in mgr.state.policy_list]),
+        "values": s.values, "rewards": s.rewards, "dones": s.dones,
+        "advantages": s.advantages, "bootstrap": s.bootstrap,
+        "actions": s.actions, "log_probs": s.log_probs,
+        "metrics": m.ring[(m.cur_buffer_offset - 1) % m.buffer_size],
+    }
+    cap = DUMP_BUDGET_BYTES // len(arrays) // 4  # float32 elements per array
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def time_call(fn, iters, stream):
@@ -399,6 +438,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed updates also run the measurements that take runs of "
+                         "their own: kernel rooflines, the separate-sim headline line and the "
+                         "CPU baseline (each can be dropped with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed update computed (parameters, rollout "
+                         "store, metrics) as DIR/<name>.npy, float32, at most 64 MB")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
@@ -446,6 +492,9 @@ def main():
     RolloutManager.rollout_kernel = args.rollout_kernel
     RolloutManager.fused_gae = not args.no_fused_gae
     if args.emulate_world > 1:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs writes the plain run's outputs: not with "
+                             "--emulate-world")
         return emulate_world(args)
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -494,6 +543,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(mgr, args.dump_outputs)
     total_steps = total * T * args.steps
     value = total_steps / elapsed
     ms = elapsed / args.steps * 1e3
@@ -540,10 +591,10 @@ def main():
             "ms_per_update_median": per_update[len(per_update) // 2],
             "ms_per_update_min": per_update[0], "ms_per_update_max": per_update[-1],
         }
-    if rank == 0 and not args.no_roofline and args.config != "lstm":
+    if rank == 0 and args.full and not args.no_roofline and args.config != "lstm":
         result["roofline"], result["kernels"] = kernel_rooflines(mgr, dev, n_rank)
-    if rank == 0 and world == 1 and not args.no_separate_sim_line and args.config == "headline" \
-            and not args.separate_sim:
+    if rank == 0 and world == 1 and args.full and not args.no_separate_sim_line \
+            and args.config == "headline" and not args.separate_sim:
         # the same job with the synthetic sim's step as its own launch between
         # the policy launches, the path a user sim plugin takes (sim_fns 'step')
         del mgr
@@ -553,7 +604,8 @@ def main():
         result["separate_sim_ms_per_update"] = _time_updates(m2, max(args.steps // 2, 3),
                                                              args.warmup) * 1e3
         del m2
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config in ("headline", "b1"):
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline \
+            and args.config in ("headline", "b1"):
         result["cpu_baseline"] = cpu_baseline()
     if rank == 0:
         print(json.dumps(result))

@@ -16,11 +16,11 @@ run() {
     echo "$name rc=$rc"
     if [ $rc -ne 0 ]; then tail -n 5 "$O/$name.err"; exit $rc; fi
 }
-run bench_headline 420 python bench.py --steps 20 --warmup 3
+run bench_headline 420 python bench.py --full --steps 20 --warmup 3
 run bench_headline_nofusedgae 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline --no-fused-gae
 run bench_headline2 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-roofline
-run prof_headline 420 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline
-run bench_b1 300 python bench.py --config b1 --steps 20 --warmup 3 --no-cpu-baseline
+run prof_headline 420 rocprofv3 --kernel-trace --stats -d $O/prof_headline -o run --output-format csv -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline
+run bench_b1 300 python bench.py --full --config b1 --steps 20 --warmup 3 --no-cpu-baseline
 run bench_twohot 300 python bench.py --critic twohot --steps 10 --warmup 3 --no-cpu-baseline --no-roofline
 run bench_lstm 300 python bench.py --config lstm --steps 10 --warmup 3 --no-cpu-baseline
 run bench_lstm_c2 300 python bench.py --config lstm --bptt-chunks 2 --steps 10 --warmup 3 --no-cpu-baseline

@@ -7,7 +7,7 @@ cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out/pmc
 export TMPDIR=/tmp
 KRE=${KRE:-ppo_step|wgrad|policy_step|gae}
-ARGS="--steps ${STEPS:-2} --warmup 1 --no-graph --no-cpu-baseline --no-roofline ${BENCH_ARGS:-}"
+ARGS="--full --steps ${STEPS:-2} --warmup 1 --no-graph --no-cpu-baseline --no-roofline ${BENCH_ARGS:-}"
 i=0
 while read -r line; do
   [ -z "$line" ] && continue

@@ -12,7 +12,7 @@ for run in "${R[@]}"; do
   name=${run%%=*}; rest=${run#*=}; v=${rest%%:*}; a=${rest#*:}
   lib=$PWD/madrona-learn_amd/madrona_learn/_lib/libmlearn.so
   [ "$v" != base ] && lib=$PWD/madrona-learn_amd/variants/libmlearn_$v.so
-  MADRONA_LEARN_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$name -o run --output-format csv -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-roofline $a > $O/$name.log 2>&1
+  MADRONA_LEARN_LIB=$lib timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/$name -o run --output-format csv -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-roofline $a > $O/$name.log 2>&1
   rc=$?; if [ $rc -ne 0 ]; then echo "$name rc=$rc"; tail -5 $O/$name.log; exit $rc; fi
   f=$(find $O/$name -name "*kernel_stats.csv" | head -1)
   python - "$f" "$name" <<'PY'

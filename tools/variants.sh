@@ -4,6 +4,8 @@
 set -u
 cd "${GRAFT_REPO_ROOT:-$(dirname "$0")/..}"
 mkdir -p gpurun_out
+# the roofline / kernels fields read below are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS:-}"
 for v in ${VARIANTS}; do
   if [ "$v" = base ]; then lib=madrona-learn_amd/madrona_learn/_lib/libmlearn.so
   else lib=madrona-learn_amd/variants/libmlearn_$v.so; fi
