@@ -25,6 +25,7 @@ import torch
 from oracle import lstm_ref as lref
 from oracle import native as onat
 from oracle import ppo_ref as ref
+from tests.action_check import check_actions
 from tests.bf16_bound import check_bf16_update
 
 pytestmark = pytest.mark.gpu
@@ -151,13 +152,7 @@ def _check_window(s, mgr, env, p0, lay, e0, cfg):
     _check_store(s, ro, c)
     gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, e0, 32, 26) for t in range(T)])
     noisy = ro["logits"] + gum
-    off = 0
-    for g, nb in enumerate(BUCKETS):
-        sl = noisy[..., off:off + nb]
-        srt = np.sort(sl, -1)
-        clear = (srt[..., -1] - srt[..., -2]) > 1e-2
-        assert np.array_equal(np.argmax(sl, -1)[clear], acts[..., g][clear]), (e0, g)
-        off += nb
+    check_actions(noisy, acts, BUCKETS, 1e-2, f"window {e0}")
 
 
 @pytest.mark.timeout(600)
@@ -428,13 +423,7 @@ def _replay_windows(mgr, env, cfg, windows, critic_bins=1):
         gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, e0, 32, 26)
                         for t in range(T)])
         noisy = ro["logits"] + gum
-        off = 0
-        for g, nb in enumerate(BUCKETS):
-            sl = noisy[..., off:off + nb]
-            srt = np.sort(sl, -1)
-            clear = (srt[..., -1] - srt[..., -2]) > 1e-2
-            assert np.array_equal(np.argmax(sl, -1)[clear], acts[..., g][clear]), (e0, g)
-            off += nb
+        check_actions(noisy, acts, BUCKETS, 1e-2, f"window {e0}")
         # the env after the rollout (the row split writes it once, at the end)
         assert np.array_equal(env.obs[c].cpu().numpy(), oenv.obs), e0
         assert np.array_equal(env.state[c].cpu().numpy(), oenv.state), e0
