@@ -30,6 +30,10 @@ int device_cus();
 // hipFuncAttributeMaxDynamicSharedMemorySize of fn, set once per (function,
 // device) outside graph capture; MLEARN_EHIP with a message when refused
 int set_lds_attr(const void* fn, int bytes, const char* what);
+// Resident slots of fn on the current device (workgroups of `threads` threads
+// and `lds` dynamic LDS bytes per CU x device_cus()), queried once per
+// (function, device, lds) outside graph capture; 0 when a query fails
+int64_t resident_slots(const void* fn, int threads, size_t lds);
 
 #define ML_REQUIRE(cond, ...)                                   \
     do {                                                        \

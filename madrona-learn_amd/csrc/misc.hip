@@ -12,8 +12,10 @@
 #include "common.h"
 
 #include <atomic>
+#include <map>
 #include <mutex>
 #include <set>
+#include <tuple>
 #include <utility>
 #include "dists.h"
 #include "env.h"
@@ -71,6 +73,24 @@ int set_lds_attr(const void* fn, int bytes, const char* what) {
     }
     done.insert({fn, dev});
     return MLEARN_OK;
+}
+
+int64_t resident_slots(const void* fn, int threads, size_t lds) {
+    static std::mutex mu;
+    static std::map<std::tuple<const void*, int, size_t>, int> per_cu;  // 0: the query failed
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return 0;
+    std::lock_guard<std::mutex> lock(mu);
+    auto it = per_cu.find({fn, dev, lds});
+    if (it == per_cu.end()) {
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, fn, threads, lds) != hipSuccess) {
+            (void)hipGetLastError();
+            n = 0;
+        }
+        it = per_cu.emplace(std::make_tuple(fn, dev, lds), n).first;
+    }
+    return (int64_t)it->second * device_cus();
 }
 
 static inline int grid_for(int64_t n, int block, int cap = 1 << 20) {

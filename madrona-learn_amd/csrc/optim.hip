@@ -10,6 +10,7 @@
 // block re-reduces identically (deterministic, no finishing launches).
 
 #include "common.h"
+#include "dispatch.h"
 #include "rowtile.h"
 
 namespace ml {
@@ -622,34 +623,23 @@ static int64_t optim_bar_offset(const LayoutK& k) {
 }
 static int64_t optim_ws_doubles(const LayoutK& k) { return optim_bar_offset(k) + kBarWords; }
 
-// Projection slot counts with a project_kernel instantiation: 2 L (trunk
-// kernels + LayerNorms, L <= MLEARN_MAX_LAYERS) and 2 L + 8 (the LSTM gate
-// kernels); optim_launch checks nslot against it before anything launches.
-constexpr int kMaxProjSlots = 16;
+// Projection slot counts with a project_kernel instantiation (dispatch_slots);
+// optim_launch checks nslot against it before anything launches.
 static_assert(kMaxSlots <= kMaxProjSlots, "a projection slot count has no project_kernel instantiation");
 static bool project_slots_ok(int nslot) { return nslot >= 2 && nslot <= kMaxProjSlots && nslot % 2 == 0; }
 
 template <typename T>
 static void launch_project(int nslot, dim3 grid, hipStream_t s, const LayoutK& Lk, const CopiesK& C,
                            const mlearn_optim_state* st, const double* ppart, int ablk) {
-#define ML_PROJ(NS)                                                                            \
-    case NS:                                                                                   \
-        hipLaunchKernelGGL((project_kernel<T, NS>), grid, dim3(256), 0, s, Lk, C, st->params, \
-                           st->init_norms, ppart, ablk, st->normalize_params,                  \
-                           st->normalize_layernorms, st->step);                                \
-        break;
-    switch (nslot) {
-        ML_PROJ(2)
-        ML_PROJ(4)
-        ML_PROJ(6)
-        ML_PROJ(8)
-        ML_PROJ(10)
-        ML_PROJ(12)
-        ML_PROJ(14)
-        ML_PROJ(16)
-        default: break;  // unreachable: project_slots_ok(nslot) was required before any launch
-    }
-#undef ML_PROJ
+    dispatch_slots(
+        nslot,
+        [&](auto ns) {
+            hipLaunchKernelGGL((project_kernel<T, ns>), grid, dim3(256), 0, s, Lk, C, st->params,
+                               st->init_norms, ppart, ablk, st->normalize_params,
+                               st->normalize_layernorms, st->step);
+            return 0;
+        },
+        [] { return 0; });  // unreachable: project_slots_ok(nslot) was required before any launch
 }
 
 // ---------------------------------------------------------------------------
@@ -762,31 +752,22 @@ template <typename T>
 static int launch_fused(int nslot, int64_t nit, int norm, const LayoutK& Lk, const CopiesK& C,
                         const mlearn_optim_state* st, const double* gpart_in, int64_t npart_in,
                         double* gpart, double* ppart, int ablk, uint64_t* bar, hipStream_t s) {
-#define ML_FUSED(NS)                                                                              \
-    case NS:                                                                                      \
-        if (nit <= 1)                                                                             \
-            return norm ? launch_fused_k<T, NS, 1, true>(Lk, C, st, gpart_in, npart_in, gpart,    \
-                                                         ppart, ablk, bar, s)                     \
-                        : launch_fused_k<T, NS, 1, false>(Lk, C, st, gpart_in, npart_in, gpart,   \
-                                                          ppart, ablk, bar, s);                   \
-        return norm ? launch_fused_k<T, NS, 8, true>(Lk, C, st, gpart_in, npart_in, gpart, ppart, \
-                                                     ablk, bar, s)                                \
-                    : launch_fused_k<T, NS, 8, false>(Lk, C, st, gpart_in, npart_in, gpart,       \
-                                                      ppart, ablk, bar, s);
-    switch (nslot) {
-        ML_FUSED(2)
-        ML_FUSED(4)
-        ML_FUSED(6)
-        ML_FUSED(8)
-        ML_FUSED(10)
-        ML_FUSED(12)
-        ML_FUSED(14)
-        ML_FUSED(16)
-        default: break;
-    }
-#undef ML_FUSED
-    set_error("optim_step: %d projection slots", nslot);
-    return MLEARN_EINVAL;
+    return dispatch_slots(
+        nslot,
+        [&](auto ns) {
+            constexpr int NS = ns;
+            return dispatch_bool(norm != 0, [&](auto nm) {
+                constexpr bool NORM = nm;
+                return nit <= 1 ? launch_fused_k<T, NS, 1, NORM>(Lk, C, st, gpart_in, npart_in,
+                                                                 gpart, ppart, ablk, bar, s)
+                                : launch_fused_k<T, NS, 8, NORM>(Lk, C, st, gpart_in, npart_in,
+                                                                 gpart, ppart, ablk, bar, s);
+            });
+        },
+        [&] {
+            set_error("optim_step: %d projection slots", nslot);
+            return (int)MLEARN_EINVAL;
+        });
 }
 
 }  // namespace ml
@@ -835,19 +816,19 @@ static int optim_launch(const LayoutK& Lk, const CopiesK& C, int dtype,
                    st->step && workspace,
                "optim_step: null pointer");
     ML_REQUIRE(st->max_grad_norm > 0 && st->lr >= 0, "optim_step: bad hyperparameters");
-    ML_REQUIRE(project_slots_ok(2 * Lk.L + (Lk.lstm_H ? 8 : 0)),
-               "optim_step: %d projection slots (layers %d) have no projection kernel",
-               2 * Lk.L + (Lk.lstm_H ? 8 : 0), Lk.L);
+    const int nslot = 2 * Lk.L + (Lk.lstm_H ? 8 : 0);
+    ML_REQUIRE(project_slots_ok(nslot),
+               "optim_step: %d projection slots (layers %d) have no projection kernel", nslot, Lk.L);
     const int64_t nblk = (Lk.total + 255) / 256;
     const int ablk = (int)(nblk < kAdamBlocks ? nblk : kAdamBlocks);
+    const int64_t nit = (Lk.total + (int64_t)ablk * 256 - 1) / ((int64_t)ablk * 256);
     double* gpart = (double*)workspace;
     double* ppart = gpart + kNormBlocks;
     const double* norm_part = gpart;
     int64_t nparts = kNormBlocks;
     ML_REQUIRE(st->launch_form >= 0 && st->launch_form <= 2, "optim_step: launch_form %d",
                st->launch_form);
-    const bool fused_fits =
-        fused_ok(ablk, (Lk.total + (int64_t)ablk * 256 - 1) / ((int64_t)ablk * 256));
+    const bool fused_fits = fused_ok(ablk, nit);
     ML_REQUIRE(st->launch_form != 2 || fused_fits,
                "optim_step: the fused launch needs %d workgroups (one per CU) on %d CUs",
                (ablk + kFusedVB - 1) / kFusedVB, device_cus());
@@ -867,24 +848,22 @@ static int optim_launch(const LayoutK& Lk, const CopiesK& C, int dtype,
         hipLaunchKernelGGL(sumsq_partial_kernel, dim3(kNormBlocks), dim3(256), 0, s, st->grads,
                            Lk.total, gpart);
     }
-    const int nslot = 2 * Lk.L + (Lk.lstm_H ? 8 : 0);
-    const int64_t nit = (Lk.total + (int64_t)ablk * 256 - 1) / ((int64_t)ablk * 256);
     if (fused) {
         const int norm = st->grad_sumsq_part ? 0 : 1;
-        if (dtype == MLEARN_DTYPE_BF16)
-            return launch_fused<bf16>(nslot, nit, norm, Lk, C, st, norm_part, nparts, gpart, ppart,
-                                      ablk, (uint64_t*)(gpart + optim_bar_offset(Lk)), s);
-        return launch_fused<float>(nslot, nit, norm, Lk, C, st, norm_part, nparts, gpart, ppart,
-                                   ablk, (uint64_t*)(gpart + optim_bar_offset(Lk)), s);
+        return dispatch_dtype(dtype, [&](auto t) {
+            return launch_fused<tag_t<decltype(t)>>(nslot, nit, norm, Lk, C, st, norm_part, nparts,
+                                                    gpart, ppart, ablk,
+                                                    (uint64_t*)(gpart + optim_bar_offset(Lk)), s);
+        });
     }
     auto adam = nit <= 1 ? adam_kernel<1> : nit <= 2 ? adam_kernel<2> : nit <= 4 ? adam_kernel<4> : adam_kernel<8>;
     hipLaunchKernelGGL(adam, dim3((unsigned)ablk), dim3(256), 0, s, Lk, st->params,
                        st->grads, st->adam_m, st->adam_v, (const int32_t*)st->step, norm_part,
                        nparts, st->lr, st->b1, st->b2, st->eps, st->max_grad_norm, ppart);
-    if (dtype == MLEARN_DTYPE_BF16)
-        launch_project<bf16>(nslot, dim3((unsigned)nblk), s, Lk, C, st, (const double*)ppart, ablk);
-    else
-        launch_project<float>(nslot, dim3((unsigned)nblk), s, Lk, C, st, (const double*)ppart, ablk);
+    dispatch_dtype(dtype, [&](auto t) {
+        launch_project<tag_t<decltype(t)>>(nslot, dim3((unsigned)nblk), s, Lk, C, st,
+                                           (const double*)ppart, ablk);
+    });
     return check_launch("optim_step");
 }
 
@@ -893,10 +872,9 @@ static int sync_launch(const LayoutK& Lk, const CopiesK& C, int dtype, const flo
     ML_REQUIRE(params, "sync_weights: null params");
     int64_t n = Lk.total > (int64_t)Lk.HC * Lk.H ? Lk.total : (int64_t)Lk.HC * Lk.H;
     unsigned g = (unsigned)((n + 255) / 256);
-    if (dtype == MLEARN_DTYPE_BF16)
-        hipLaunchKernelGGL(sync_kernel<bf16>, dim3(g), dim3(256), 0, s, Lk, C, params);
-    else
-        hipLaunchKernelGGL(sync_kernel<float>, dim3(g), dim3(256), 0, s, Lk, C, params);
+    dispatch_dtype(dtype, [&](auto t) {
+        hipLaunchKernelGGL(sync_kernel<tag_t<decltype(t)>>, dim3(g), dim3(256), 0, s, Lk, C, params);
+    });
     return check_launch("sync_weights");
 }
 

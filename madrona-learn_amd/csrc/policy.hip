@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "common.h"
+#include "dispatch.h"
 #include "dists.h"
 #include "env.h"
 #include "rowtile.h"
@@ -782,6 +783,14 @@ static int launch_rollout16_pop(const PopEntry* pop, int npol, int64_t N, uint32
     return check_launch("policy_rollout_env_pop (row split)");
 }
 
+constexpr int kPolLdsLimit = 128 * 1024;  // dynamic-LDS limit the feature-split policy kernels ask for
+
+// f(T, H, HC, RNN) for a validated policy (recurrent when lstm is given)
+template <typename F>
+static auto dispatch_policy(const mlearn_mlp_policy& p, const mlearn_lstm* lstm, F&& f) {
+    return dispatch_policy(p.dtype, p.hidden, head_cols(p), lstm != nullptr, f);
+}
+
 template <typename T, int H, bool RNN, int HC, int MAXW = ML_POL_MAXW>
 static size_t policy_step_lds(int L) {
     typedef PolCfg<H, MAXW> C;
@@ -799,12 +808,8 @@ static int launch_policy_step(const PolicyK& P, const float* obs, int64_t N, voi
                               const EnvK& env, hipStream_t s) {
     const size_t lds = policy_step_lds<T, H, RNN, HC, pol_maxw<RNN>()>(P.L);
     auto kern = policy_step_kernel<T, H, RNN, HC>;
-    static bool attr_set = false;  // once per instantiation (kept out of graph capture)
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  128 * 1024);
-        attr_set = true;
-    }
+    // (once per instantiation and device, kept out of graph capture)
+    if (int rc = set_lds_attr((const void*)kern, kPolLdsLimit, "policy_rollout_step")) return rc;
     const int grid = (int)((N + 31) / 32);
 #ifdef ML_STAMPS
     EvalK evs = ev;
@@ -825,22 +830,12 @@ template <typename T, int H, bool RNN, int HC>
 static int64_t rollout_grid(int L, int64_t N, int max_wg) {
     constexpr int NT = pol_threads<H, RNN>();
     const size_t lds = policy_step_lds<T, H, RNN, HC, pol_maxw<RNN>()>(L);
-    auto kern = policy_rollout_kernel<T, H, RNN, HC>;
-    static bool attr_set = false;
-    static int per_cu = 0, cus = 0;
-    if (!attr_set) {  // once per instantiation (kept out of graph capture)
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  128 * 1024);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NT, lds) !=
-                hipSuccess)
-            per_cu = cus = 0;
-        attr_set = true;
-    }
+    const void* kern = (const void*)policy_rollout_kernel<T, H, RNN, HC>;
+    // (the occupancy answer needs the raised limit; a refusal reads as no answer
+    // here, and the launcher reports it)
+    if (set_lds_attr(kern, kPolLdsLimit, "policy_rollout_env")) return -1;
     const int64_t tiles = (N + 31) / 32;
-    int64_t slots = (int64_t)per_cu * cus;
+    int64_t slots = resident_slots(kern, NT, lds);
     if (max_wg < 0 || slots <= 0) return -1;
     if (max_wg > 0 && max_wg < slots) slots = max_wg;
     // one workgroup per resident slot, tiles dealt round-robin (tile =
@@ -862,6 +857,10 @@ static int launch_policy_rollout(const PolicyK& P, const float* obs, int64_t N, 
                                  const LstmK& R, const CarryK& cy, const EnvK& env, hipStream_t s) {
     constexpr int NT = pol_threads<H, RNN>();
     const size_t lds = policy_step_lds<T, H, RNN, HC, pol_maxw<RNN>()>(P.L);
+    // (once per instantiation and device, kept out of graph capture)
+    if (int rc = set_lds_attr((const void*)policy_rollout_kernel<T, H, RNN, HC>, kPolLdsLimit,
+                              "policy_rollout_env"))
+        return rc;
     const int64_t grid = rollout_grid<T, H, RNN, HC>(P.L, N, rk.max_wg);
     if (grid > 0) {
         hipLaunchKernelGGL((policy_rollout_kernel<T, H, RNN, HC>), dim3((unsigned)grid), dim3(NT),
@@ -901,21 +900,10 @@ template <typename T, int H, bool RNN, int HC>
 static int64_t rollout_pop_grid(int L, int64_t tiles, int max_wg) {
     constexpr int NT = pol_threads<H, RNN>();
     const size_t lds = policy_step_lds<T, H, RNN, HC, pol_maxw<RNN>()>(L);
-    auto kern = policy_rollout_pop_kernel<T, H, RNN, HC>;
-    static bool attr_set = false;
-    static int per_cu = 0, cus = 0;
-    if (!attr_set) {  // once per instantiation (kept out of graph capture)
-        (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  128 * 1024);
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess ||
-            hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)kern, NT, lds) !=
-                hipSuccess)
-            per_cu = cus = 0;
-        attr_set = true;
-    }
-    int64_t slots = (int64_t)per_cu * cus;
+    const void* kern = (const void*)policy_rollout_pop_kernel<T, H, RNN, HC>;
+    // (as rollout_grid: a refused limit reads as no answer, the launcher reports it)
+    if (set_lds_attr(kern, kPolLdsLimit, "policy_rollout_env_pop")) return -1;
+    int64_t slots = resident_slots(kern, NT, lds);
     if (slots <= 0) return -1;
     // max_wg > 0 caps the grid (tiles of several policies in series per
     // workgroup, each move to another policy's tile restaging its parameters)
@@ -929,6 +917,10 @@ static int launch_policy_rollout_pop(int L, const PopEntry* pop, int npol, int64
                                      hipStream_t s) {
     constexpr int NT = pol_threads<H, RNN>();
     const size_t lds = policy_step_lds<T, H, RNN, HC, pol_maxw<RNN>()>(L);
+    // (once per instantiation and device, kept out of graph capture)
+    if (int rc = set_lds_attr((const void*)policy_rollout_pop_kernel<T, H, RNN, HC>, kPolLdsLimit,
+                              "policy_rollout_env_pop"))
+        return rc;
     const int64_t grid =
         rollout_pop_grid<T, H, RNN, HC>(L, (int64_t)npol * ((N + 31) / 32), max_wg);
     ML_REQUIRE(grid > 0, "policy_rollout_env_pop: no occupancy answer for the population kernel");
@@ -993,29 +985,11 @@ static int rollout_step_entry(const mlearn_mlp_policy* policy, const mlearn_lstm
     }
     PolicyK P = make_policy_k(*policy);
     hipStream_t s = S(stream);
-#define ML_LAUNCH_HC(T, HH, HC)                                                                 \
-    (lstm ? launch_policy_step<T, HH, true, HC>(P, obs, N, obs_store, actions, log_probs, values, \
-                                                k0, k1, step_ctr, step, env_offset, sample, pk, R, \
-                                                cy, ev, ek, s)                                    \
-          : launch_policy_step<T, HH, false, HC>(P, obs, N, obs_store, actions, log_probs, values, \
-                                                 k0, k1, step_ctr, step, env_offset, sample, pk, R, \
-                                                 cy, ev, ek, s))
-#define ML_LAUNCH(T, HH) \
-    (P.HC == MLEARN_HEAD_COLS ? ML_LAUNCH_HC(T, HH, MLEARN_HEAD_COLS) : ML_LAUNCH_HC(T, HH, MLEARN_HEAD_COLS_MAX))
-#define ML_DISPATCH(T)                      \
-    switch (policy->hidden) {               \
-        case 64: return ML_LAUNCH(T, 64);   \
-        case 128: return ML_LAUNCH(T, 128); \
-        default: return ML_LAUNCH(T, 256);  \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
-#undef ML_LAUNCH
-#undef ML_LAUNCH_HC
+    return dispatch_policy(*policy, lstm, [&](auto t, auto h, auto hc, auto rnn) {
+        return launch_policy_step<tag_t<decltype(t)>, h, rnn, hc>(
+            P, obs, N, obs_store, actions, log_probs, values, k0, k1, step_ctr, step, env_offset,
+            sample, pk, R, cy, ev, ek, s);
+    });
 }
 
 }  // namespace ml
@@ -1107,25 +1081,19 @@ extern "C" int mlearn_policy_rollout_env(const mlearn_mlp_policy* policy, const 
     ML_REQUIRE(!out->advantages || out->ld == N,
                "policy_rollout_env: advantages need ld == N (ld %lld, N %lld)",
                (long long)out->ld, (long long)N);
+    RollK rk2 = rk;
+    int rc2;
     if (r16 && out->policy_kernel != 1) {
-        RollK rk2 = rk;
         if (out->advantages && out->T <= 32) rk2.adv = out->advantages;  // fused GAE
-        const int rc2 = launch_rollout16(P, obs, N, rk2, k0, k1, step_ctr, env_offset, ek, s);
-        if (rc2 || !out->advantages || rk2.adv) return rc2;
-        return mlearn_gae_f32(out->rewards, out->values, out->dones, out->bootstrap,
-                              out->advantages, nullptr, out->T, N, out->gae_gamma,
-                              out->gae_gamma_lambda, stream);
+        rc2 = launch_rollout16(P, obs, N, rk2, k0, k1, step_ctr, env_offset, ek, s);
+    } else {
+        rc2 = feature_split_rollout(policy, lstm, P, R, cy, obs, N, rk, k0, k1, step_ctr,
+                                    env_offset, ek, s);
     }
-    if (out->advantages) {  // the feature-split rollout, then GAE as its own launch
-        const int rc2 = feature_split_rollout(policy, lstm, P, R, cy, obs, N, rk, k0, k1, step_ctr,
-                                              env_offset, ek, s);
-        if (rc2) return rc2;
-        return mlearn_gae_f32(out->rewards, out->values, out->dones, out->bootstrap,
-                              out->advantages, nullptr, out->T, N, out->gae_gamma,
-                              out->gae_gamma_lambda, stream);
-    }
-    return feature_split_rollout(policy, lstm, P, R, cy, obs, N, rk, k0, k1, step_ctr, env_offset,
-                                 ek, s);
+    // GAE as its own launch, unless the row-split rollout fused it
+    if (rc2 || !out->advantages || rk2.adv) return rc2;
+    return mlearn_gae_f32(out->rewards, out->values, out->dones, out->bootstrap, out->advantages,
+                          nullptr, out->T, N, out->gae_gamma, out->gae_gamma_lambda, stream);
 }
 
 // The feature-split whole-rollout launch (policy_rollout_kernel) for the
@@ -1135,27 +1103,10 @@ static int feature_split_rollout(const mlearn_mlp_policy* policy, const mlearn_l
                                  const float* obs, int64_t N, const RollK& rk, uint32_t k0,
                                  uint32_t k1, const uint64_t* step_ctr, uint32_t env_offset,
                                  const EnvK& ek, hipStream_t s) {
-#define ML_LAUNCH_HC(T, HH, HC)                                                                 \
-    (lstm ? launch_policy_rollout<T, HH, true, HC>(P, obs, N, rk, k0, k1, step_ctr, env_offset, R, \
-                                                   cy, ek, s)                                     \
-          : launch_policy_rollout<T, HH, false, HC>(P, obs, N, rk, k0, k1, step_ctr, env_offset, R, \
-                                                    cy, ek, s))
-#define ML_LAUNCH(T, HH) \
-    (P.HC == MLEARN_HEAD_COLS ? ML_LAUNCH_HC(T, HH, MLEARN_HEAD_COLS) : ML_LAUNCH_HC(T, HH, MLEARN_HEAD_COLS_MAX))
-#define ML_DISPATCH(T)                      \
-    switch (policy->hidden) {               \
-        case 64: return ML_LAUNCH(T, 64);   \
-        case 128: return ML_LAUNCH(T, 128); \
-        default: return ML_LAUNCH(T, 256);  \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
-#undef ML_LAUNCH
-#undef ML_LAUNCH_HC
+    return dispatch_policy(*policy, lstm, [&](auto t, auto h, auto hc, auto rnn) {
+        return launch_policy_rollout<tag_t<decltype(t)>, h, rnn, hc>(P, obs, N, rk, k0, k1, step_ctr,
+                                                                     env_offset, R, cy, ek, s);
+    });
 }
 
 
@@ -1218,33 +1169,16 @@ extern "C" int mlearn_policy_rollout_env_pop(const mlearn_mlp_policy* policy0,
     ML_REQUIRE(pop && num_policies >= 1 && N >= 1 && step_ctr,
                "policy_rollout_env_pop: null pop / step counter, or no work");
     ML_REQUIRE(max_workgroups >= 0, "policy_rollout_env_pop: max_workgroups < 0");
-    const int L = policy0->num_layers, HC = head_cols(*policy0);
+    const int L = policy0->num_layers;
     const PopEntry* e = (const PopEntry*)pop;
     hipStream_t s = S(stream);
     if (rollout16_pop_eligible(make_policy_k(*policy0), N, num_policies, max_workgroups,
                                policy0->dtype == MLEARN_DTYPE_BF16, lstm0 != nullptr))
         return launch_rollout16_pop(e, num_policies, N, k0, k1, step_ctr, s);
-#define ML_POP_HC(T, HH, HCC)                                                                   \
-    (lstm0 ? launch_policy_rollout_pop<T, HH, true, HCC>(L, e, num_policies, N, k0, k1, step_ctr, \
-                                                       max_workgroups, s)                     \
-           : launch_policy_rollout_pop<T, HH, false, HCC>(L, e, num_policies, N, k0, k1, step_ctr, \
-                                                        max_workgroups, s))
-#define ML_POP(T, HH) \
-    (HC == MLEARN_HEAD_COLS ? ML_POP_HC(T, HH, MLEARN_HEAD_COLS) : ML_POP_HC(T, HH, MLEARN_HEAD_COLS_MAX))
-#define ML_DISPATCH(T)                   \
-    switch (policy0->hidden) {           \
-        case 64: return ML_POP(T, 64);   \
-        case 128: return ML_POP(T, 128); \
-        default: return ML_POP(T, 256);  \
-    }
-    if (policy0->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
-#undef ML_POP
-#undef ML_POP_HC
+    return dispatch_policy(*policy0, lstm0, [&](auto t, auto h, auto hc, auto rnn) {
+        return launch_policy_rollout_pop<tag_t<decltype(t)>, h, rnn, hc>(
+            L, e, num_policies, N, k0, k1, step_ctr, max_workgroups, s);
+    });
 }
 
 extern "C" int32_t mlearn_policy_rollout_pop_kernel(const mlearn_mlp_policy* policy,
@@ -1267,53 +1201,21 @@ extern "C" int64_t mlearn_policy_rollout_pop_workgroups(const mlearn_mlp_policy*
     if ((lstm ? validate_lstm(policy, lstm) : validate_policy(policy)) || N < 1 ||
         num_policies < 1 || max_workgroups < 0)
         return -1;
-    const int HC = head_cols(*policy), L = policy->num_layers;
+    const int L = policy->num_layers;
     const int64_t tiles = (int64_t)num_policies * ((N + 31) / 32);
-#define ML_GRID_HC(T, HH, HCC) \
-    (lstm ? rollout_pop_grid<T, HH, true, HCC>(L, tiles, max_workgroups) \
-          : rollout_pop_grid<T, HH, false, HCC>(L, tiles, max_workgroups))
-#define ML_GRID(T, HH) \
-    (HC == MLEARN_HEAD_COLS ? ML_GRID_HC(T, HH, MLEARN_HEAD_COLS) : ML_GRID_HC(T, HH, MLEARN_HEAD_COLS_MAX))
-#define ML_DISPATCH(T)                    \
-    switch (policy->hidden) {             \
-        case 64: return ML_GRID(T, 64);   \
-        case 128: return ML_GRID(T, 128); \
-        default: return ML_GRID(T, 256);  \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
-#undef ML_GRID
-#undef ML_GRID_HC
+    return dispatch_policy(*policy, lstm, [&](auto t, auto h, auto hc, auto rnn) {
+        return rollout_pop_grid<tag_t<decltype(t)>, h, rnn, hc>(L, tiles, max_workgroups);
+    });
 }
 
 extern "C" int64_t mlearn_policy_rollout_workgroups(const mlearn_mlp_policy* policy,
                                                     const mlearn_lstm* lstm, int64_t N,
                                                     int32_t max_workgroups) {
     if ((lstm ? validate_lstm(policy, lstm) : validate_policy(policy)) || N < 1) return -1;
-    const int HC = head_cols(*policy), L = policy->num_layers;
-#define ML_GRID_HC(T, HH, HCC) \
-    (lstm ? rollout_grid<T, HH, true, HCC>(L, N, max_workgroups) \
-          : rollout_grid<T, HH, false, HCC>(L, N, max_workgroups))
-#define ML_GRID(T, HH) \
-    (HC == MLEARN_HEAD_COLS ? ML_GRID_HC(T, HH, MLEARN_HEAD_COLS) : ML_GRID_HC(T, HH, MLEARN_HEAD_COLS_MAX))
-#define ML_DISPATCH(T)                    \
-    switch (policy->hidden) {             \
-        case 64: return ML_GRID(T, 64);   \
-        case 128: return ML_GRID(T, 128); \
-        default: return ML_GRID(T, 256);  \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
-#undef ML_GRID
-#undef ML_GRID_HC
+    const int L = policy->num_layers;
+    return dispatch_policy(*policy, lstm, [&](auto t, auto h, auto hc, auto rnn) {
+        return rollout_grid<tag_t<decltype(t)>, h, rnn, hc>(L, N, max_workgroups);
+    });
 }
 
 extern "C" int32_t mlearn_policy_rollout_kernel(const mlearn_mlp_policy* policy,

@@ -19,6 +19,7 @@
 //   tl = f / mb, m = f % mb, seq = mb_seq[m], c = seq / N, b = seq % N,
 //   store row = (c * bptt + tl) * N + b.
 
+#include "dispatch.h"
 #include "ppo_defs.h"
 #include "r16_common.h"
 
@@ -668,32 +669,32 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
 #define ML_STEP_RTW 1  // row tiles per workgroup of the fused MLP step (kFused; 2 measured slower)
 #endif
 template <typename T, int H, int L, int MODE, int HC>
-static void launch_step_hc(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
-                           int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
-                           hipStream_t s, const RecK& rec) {
+static int launch_step_hc(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
+                          int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
+                          hipStream_t s, const RecK& rec) {
     // ntiles = Mp / 32 is even (Mp is a multiple of 64)
     constexpr int RTW = (MODE == kFused && StepCfg<H>::W * ML_STEP_RTW <= 16) ? ML_STEP_RTW : 1;
     auto k = ppo_step_kernel<T, H, L, MODE, HC, RTW>;
-    static bool attr_set = false;  // once per instantiation (kept out of graph capture)
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  160 * 1024);
-        attr_set = true;
-    }
+    // (once per instantiation and device, kept out of graph capture)
+    if (int rc = set_lds_attr((const void*)k, 160 * 1024, "ppo_step")) return rc;
     const size_t lds = step_lds<T, H, L, HC, RTW>();
     const int threads = 64 * StepCfg<H>::W * RTW;
     hipLaunchKernelGGL(k, dim3(ws.ntiles / RTW), dim3(threads), lds, s, P, R, mb_seq, mb, M,
                        adv_st, hp, ws, rec);
+    return MLEARN_OK;
 }
-template <typename T, int H, int L, int MODE = kFused>
-static void launch_step(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
-                        int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
-                        hipStream_t s, const RecK& rec = RecK{}) {
-    if (P.HC == MLEARN_HEAD_COLS)
-        launch_step_hc<T, H, L, MODE, MLEARN_HEAD_COLS>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec);
-    else
-        launch_step_hc<T, H, L, MODE, MLEARN_HEAD_COLS_MAX>(P, R, mb_seq, mb, M, adv_st, hp, ws, s,
-                                                            rec);
+// The step kernel of the policy's depth and head width (MODE: the whole
+// step, or one of the recurrent update's three parts).
+template <typename T, int H, int MODE = kFused>
+static int launch_step(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
+                       int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
+                       hipStream_t s, const RecK& rec = RecK{}) {
+    return dispatch_layers(P.L, [&](auto l) {
+        constexpr int L = l;
+        return dispatch_head(P.HC, [&](auto hc) {
+            return launch_step_hc<T, H, L, MODE, hc>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec);
+        });
+    });
 }
 
 // ---------------------------------------------------------------------------
@@ -1356,15 +1357,12 @@ __device__ inline void loss_block(const WsK& ws, const HpK& hp, int64_t M, int K
 // The gradient launches: weight-gradient tiles, column partials and loss
 // metrics; then the reduction into grad, one 64-parameter chunk per block.
 template <typename T>
-static void launch_wgrad(const WgJobs& jobs, const WsK& ws, const HpK& hp, int64_t M, int K,
-                         float* loss_out, const LayoutK& Lk, float* grad, double* sumsq,
-                         hipStream_t s) {
-    static bool attr_set = false;  // once per instantiation (kept out of graph capture)
-    if (!attr_set) {
-        (void)hipFuncSetAttribute((const void*)wgrad_kernel<T>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)WgCfg<T>::lds);
-        attr_set = true;
-    }
+static int launch_wgrad(const WgJobs& jobs, const WsK& ws, const HpK& hp, int64_t M, int K,
+                        float* loss_out, const LayoutK& Lk, float* grad, double* sumsq,
+                        hipStream_t s) {
+    // (once per instantiation and device, kept out of graph capture)
+    if (int rc = set_lds_attr((const void*)wgrad_kernel<T>, (int)WgCfg<T>::lds, "ppo_wgrad"))
+        return rc;
     const int blocks = jobs.nwg + jobs.ncol + (loss_out ? 1 : 0);
     hipLaunchKernelGGL((wgrad_kernel<T>), dim3(blocks), dim3(256), WgCfg<T>::lds, s, jobs, ws, hp, M,
                        K, loss_out);
@@ -1374,6 +1372,66 @@ static void launch_wgrad(const WgJobs& jobs, const WsK& ws, const HpK& hp, int64
 #endif
     hipLaunchKernelGGL(reduce_grads_kernel, dim3((unsigned)((Lk.total + 63) / 64)), dim3(256), 0, s,
                        Lk, ws, grad, sumsq);
+    return MLEARN_OK;
+}
+
+// The kernels' view of the hyper-parameters for M rows per minibatch.
+static int make_hp(const mlearn_ppo_hparams& h, int64_t M, int num_groups, bool metrics, HpK* out) {
+    ML_REQUIRE(h.wgrad_form >= 0 && h.wgrad_form <= 2, "ppo: wgrad_form %d", h.wgrad_form);
+    HpK hp{};
+    hp.clip = h.clip_coef;
+    hp.vcoef = h.value_loss_coef;
+    for (int i = 0; i < MLEARN_MAX_GROUPS; ++i) {
+        hp.ecoef[i] = h.entropy_coef[i];
+        hp.objw[i] = h.obj_weight[i] != 0.f ? h.obj_weight[i] : 1.f;
+    }
+    hp.norm_adv = h.normalize_advantages;
+    hp.clip_vl = h.clip_value_loss;
+    hp.norm_vals = h.normalize_values;
+    hp.huber = h.huber_value_loss;
+    hp.loss_scale = h.loss_scale;
+    hp.metrics = metrics;
+    hp.wg_form = h.wgrad_form;
+    hp.inv_s = (float)(1.0 / (double)M);
+    hp.inv_sk = (float)(1.0 / ((double)M * num_groups));
+    *out = hp;
+    return MLEARN_OK;
+}
+
+static RolloutK make_rollout_k(const mlearn_rollout_view& ro) {
+    return RolloutK{ro.obs, ro.actions, ro.log_probs, ro.advantages, ro.returns, ro.values, ro.dones,
+                    ro.T, ro.bptt_len, ro.N, ro.ld ? ro.ld : ro.N};
+}
+
+// One weight-gradient job per table row (dW = X^T Y, I x J), in slab order:
+// tiles, splits and first workgroup of each, and the launch's block counts.
+struct WgOperands {
+    int I, J;
+    const void *X, *Y;
+};
+static WgJobs make_wg_jobs(const WgOperands* tab, int n, const WsK& ws) {
+    WgJobs jobs{};
+    jobs.n = n;
+    jobs.Mp = ws.Mp;
+    int wg = 0;
+    for (int l = 0; l < n; ++l) {
+        WgJob& J = jobs.job[l];
+        J.I = tab[l].I;
+        J.J = tab[l].J;
+        J.X = tab[l].X;
+        J.Y = tab[l].Y;
+        J.out = ws.slab + ws.slab_off[l];
+        J.rps = ws.rps[l];
+        J.ti = (J.I + kWgTile - 1) / kWgTile;
+        J.tj = (J.J + kWgTile - 1) / kWgTile;
+        J.splits = ws.splits[l];
+        J.wg0 = wg;
+        wg += J.ti * J.tj * J.splits;
+    }
+    jobs.nwg = wg;
+    jobs.ncolx = (ws.CP + 255) / 256;
+    jobs.ncol = jobs.ncolx * kColChunks;
+    return jobs;
 }
 
 template <typename T, int H>
@@ -1388,25 +1446,9 @@ static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_vie
     ws.stamps = g_stamp_buf;
 #endif
     PolicyK P = make_policy_k(p);
-    RolloutK R{ro.obs, ro.actions, ro.log_probs, ro.advantages, ro.returns, ro.values, ro.dones,
-               ro.T, ro.bptt_len, ro.N, ro.ld ? ro.ld : ro.N};
-    HpK hp{};
-    hp.clip = h.clip_coef;
-    hp.vcoef = h.value_loss_coef;
-    for (int i = 0; i < MLEARN_MAX_GROUPS; ++i) {
-        hp.ecoef[i] = h.entropy_coef[i];
-        hp.objw[i] = h.obj_weight[i] != 0.f ? h.obj_weight[i] : 1.f;
-    }
-    hp.norm_adv = h.normalize_advantages;
-    hp.clip_vl = h.clip_value_loss;
-    hp.norm_vals = h.normalize_values;
-    hp.huber = h.huber_value_loss;
-    hp.loss_scale = h.loss_scale;
-    hp.metrics = loss_out != nullptr;
-    ML_REQUIRE(h.wgrad_form >= 0 && h.wgrad_form <= 2, "ppo: wgrad_form %d", h.wgrad_form);
-    hp.wg_form = h.wgrad_form;
-    hp.inv_s = (float)(1.0 / (double)M);
-    hp.inv_sk = (float)(1.0 / ((double)M * p.actions.num_groups));
+    RolloutK R = make_rollout_k(ro);
+    HpK hp;
+    if (int rc = make_hp(h, M, p.actions.num_groups, loss_out != nullptr, &hp)) return rc;
 
     const bool rows16 = rows16_eligible(P, ws.Mp, head_cols(p), p.num_layers, H,
                                         std::is_same<T, bf16>::value);
@@ -1419,39 +1461,19 @@ static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_vie
         ws.ncp = 2 * ws.ntiles;  // one column-partials row per 16-row tile
         if (rows16_cfg(ws.Mp).nt == 1) ws.nlp = 2 * ws.ntiles;  // one loss-partials row per wave
         launch_rows16(P, R, mb_seq, mb, M, adv_st, hp, ws, s);
-    } else {
-        switch (p.num_layers) {
-            case 1: launch_step<T, H, 1>(P, R, mb_seq, mb, M, adv_st, hp, ws, s); break;
-            case 2: launch_step<T, H, 2>(P, R, mb_seq, mb, M, adv_st, hp, ws, s); break;
-            case 3: launch_step<T, H, 3>(P, R, mb_seq, mb, M, adv_st, hp, ws, s); break;
-            default: launch_step<T, H, 4>(P, R, mb_seq, mb, M, adv_st, hp, ws, s); break;
-        }
+    } else if (int rc = launch_step<T, H>(P, R, mb_seq, mb, M, adv_st, hp, ws, s)) {
+        return rc;
     }
     if (step_only) return check_launch("ppo_minibatch_fwd_bwd");
+    // weight gradients: the trunk layers, then the head
     const int L = p.num_layers;
-    WgJobs jobs{};
-    jobs.n = L + 1;
-    jobs.Mp = ws.Mp;
-    int wg = 0;
-    for (int l = 0; l <= L; ++l) {
-        WgJob& J = jobs.job[l];
-        J.I = l == L ? H : (l == 0 ? p.obs_dim : H);
-        J.J = l == L ? head_cols(p) : H;
-        J.X = l == 0 ? ws.x0 : ws.a[l - 1];
-        J.Y = l == L ? ws.dhead : ws.dz[l];
-        J.out = ws.slab + ws.slab_off[l];
-        J.rps = ws.rps[l];
-        J.ti = (J.I + kWgTile - 1) / kWgTile;
-        J.tj = (J.J + kWgTile - 1) / kWgTile;
-        J.splits = ws.splits[l];
-        J.wg0 = wg;
-        wg += J.ti * J.tj * J.splits;
-    }
-    jobs.nwg = wg;
-    jobs.ncolx = (ws.CP + 255) / 256;
-    jobs.ncol = jobs.ncolx * kColChunks;
-    launch_wgrad<T>(jobs, ws, hp, M, p.actions.num_groups, loss_out, make_layout(p), grad,
-                    h.grad_sumsq_out, s);
+    WgOperands tab[MLEARN_MAX_LAYERS + 1];
+    for (int l = 0; l < L; ++l)
+        tab[l] = WgOperands{l == 0 ? p.obs_dim : H, H, l == 0 ? ws.x0 : ws.a[l - 1], ws.dz[l]};
+    tab[L] = WgOperands{H, head_cols(p), ws.a[L - 1], ws.dhead};
+    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 1, ws), ws, hp, M, p.actions.num_groups,
+                                 loss_out, make_layout(p), grad, h.grad_sumsq_out, s))
+        return rc;
     return check_launch("ppo_minibatch_grad");
 }
 
@@ -1475,38 +1497,13 @@ static int launch_minibatch_lstm(const mlearn_mlp_policy& p, const mlearn_lstm& 
     carve(p, M, (char*)wsp, &ws, &lstm, mb, &lw);
     PolicyK P = make_policy_k(p);
     LstmK RK = make_lstm_k(lstm);
-    RolloutK R{ro.obs, ro.actions, ro.log_probs, ro.advantages, ro.returns, ro.values, ro.dones,
-               ro.T, ro.bptt_len, ro.N, ro.ld ? ro.ld : ro.N};
-    HpK hp{};
-    hp.clip = h.clip_coef;
-    hp.vcoef = h.value_loss_coef;
-    for (int i = 0; i < MLEARN_MAX_GROUPS; ++i) {
-        hp.ecoef[i] = h.entropy_coef[i];
-        hp.objw[i] = h.obj_weight[i] != 0.f ? h.obj_weight[i] : 1.f;
-    }
-    hp.norm_adv = h.normalize_advantages;
-    hp.clip_vl = h.clip_value_loss;
-    hp.norm_vals = h.normalize_values;
-    hp.huber = h.huber_value_loss;
-    hp.loss_scale = h.loss_scale;
-    hp.metrics = loss_out != nullptr;
-    ML_REQUIRE(h.wgrad_form >= 0 && h.wgrad_form <= 2, "ppo: wgrad_form %d", h.wgrad_form);
-    hp.wg_form = h.wgrad_form;
-    hp.inv_s = (float)(1.0 / (double)M);
-    hp.inv_sk = (float)(1.0 / ((double)M * p.actions.num_groups));
+    RolloutK R = make_rollout_k(ro);
+    HpK hp;
+    if (int rc = make_hp(h, M, p.actions.num_groups, loss_out != nullptr, &hp)) return rc;
     const int L = p.num_layers;
     RecK rec{lw.hout, lw.dhout, lw.dfeat, lstm.head_t_nat};
-    auto step = [&](auto mode) {
-        constexpr int MODE = decltype(mode)::value;
-        switch (L) {
-            case 1: launch_step<T, H, 1, MODE>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec); break;
-            case 2: launch_step<T, H, 2, MODE>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec); break;
-            case 3: launch_step<T, H, 3, MODE>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec); break;
-            default: launch_step<T, H, 4, MODE>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec); break;
-        }
-    };
     // trunk forward over every row (the LSTM input F = A_{L-1})
-    step(std::integral_constant<int, kTrunkFwd>{});
+    if (int rc = launch_step<T, H, kTrunkFwd>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec)) return rc;
     const T* feat = (const T*)ws.a[L - 1];
     // forward scan: one launch per step over (mb / 32) x (H / 32) four-wave
     // workgroups (the input product F_t Wi inside each step)
@@ -1514,38 +1511,24 @@ static int launch_minibatch_lstm(const mlearn_mlp_policy& p, const mlearn_lstm& 
         hipLaunchKernelGGL((lstm_fwd_step4_kernel<T, H>), dim3(mb / 32, H / 32), dim3(256), 0, s, RK,
                            R, mb_seq, mb, (const T*)start_h, (const T*)start_c, lw, t, feat);
     // heads + loss from the LSTM outputs
-    step(std::integral_constant<int, kHeads>{});
+    if (int rc = launch_step<T, H, kHeads>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec)) return rc;
     // reverse scan: dh_t and dF_{t+1} per step, then dF_0 from dG_0
     const int cp0 = L * 2 * H + head_cols(p);
     for (int t = bptt - 1; t >= -1; --t)
         hipLaunchKernelGGL((lstm_bwd_step4_kernel<T, H>), dim3(mb / 32, H / 32), dim3(256), 0, s,
                            RK, R, mb_seq, mb, lw, ws.colpart, ws.CP, cp0, t);
     // trunk backward from d features
-    step(std::integral_constant<int, kTrunkBwd>{});
+    if (int rc = launch_step<T, H, kTrunkBwd>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec)) return rc;
     // weight gradients: trunk, head (from the LSTM outputs), Wi, Wh
-    WgJobs jobs{};
-    jobs.n = L + 3;
-    jobs.Mp = ws.Mp;
-    int wg = 0;
-    for (int l = 0; l < L + 3; ++l) {
-        WgJob& J = jobs.job[l];
-        J.I = l >= L ? H : (l == 0 ? p.obs_dim : H);
-        J.J = l == L ? head_cols(p) : (l > L ? 4 * H : H);
-        J.X = l == 0 ? ws.x0 : (l < L ? ws.a[l - 1] : (l == L ? lw.hout : (l == L + 1 ? (const void*)feat : lw.hin)));
-        J.Y = l < L ? ws.dz[l] : (l == L ? ws.dhead : lw.dg);
-        J.out = ws.slab + ws.slab_off[l];
-        J.rps = ws.rps[l];
-        J.ti = (J.I + kWgTile - 1) / kWgTile;
-        J.tj = (J.J + kWgTile - 1) / kWgTile;
-        J.splits = ws.splits[l];
-        J.wg0 = wg;
-        wg += J.ti * J.tj * J.splits;
-    }
-    jobs.nwg = wg;
-    jobs.ncolx = (ws.CP + 255) / 256;
-    jobs.ncol = jobs.ncolx * kColChunks;
-    launch_wgrad<T>(jobs, ws, hp, M, p.actions.num_groups, loss_out, make_layout_lstm(p, lstm),
-                    grad, h.grad_sumsq_out, s);
+    WgOperands tab[MLEARN_MAX_LAYERS + 3];
+    for (int l = 0; l < L; ++l)
+        tab[l] = WgOperands{l == 0 ? p.obs_dim : H, H, l == 0 ? ws.x0 : ws.a[l - 1], ws.dz[l]};
+    tab[L] = WgOperands{H, head_cols(p), lw.hout, ws.dhead};
+    tab[L + 1] = WgOperands{H, 4 * H, feat, lw.dg};
+    tab[L + 2] = WgOperands{H, 4 * H, lw.hin, lw.dg};
+    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 3, ws), ws, hp, M, p.actions.num_groups,
+                                 loss_out, make_layout_lstm(p, lstm), grad, h.grad_sumsq_out, s))
+        return rc;
     return check_launch("lstm_ppo_minibatch_grad");
 }
 
@@ -1584,42 +1567,42 @@ int32_t mlearn_ppo_step_kernel(const mlearn_mlp_policy* policy, int64_t rows, in
     return rows16 && requested != 1 ? 2 : 1;
 }
 
+// The argument checks the feed-forward and the recurrent update share; who
+// ("ppo" / "lstm ppo") prefixes the message.
+static int validate_minibatch(const char* who, const mlearn_mlp_policy* policy,
+                              const mlearn_rollout_view* ro, const int32_t* mb_seq,
+                              int32_t mb_size, const float* adv_stats,
+                              const mlearn_ppo_hparams* hp, const void* workspace) {
+    ML_REQUIRE(ro && mb_seq && adv_stats && hp && workspace, "%s: null pointer", who);
+    ML_REQUIRE(ro->N >= 1 && ro->N < (1ll << 31) && (int64_t)mb_size * ro->bptt_len < (1ll << 31),
+               "%s: N and rows per minibatch must be < 2^31", who);
+    ML_REQUIRE(ro->bptt_len >= 1 && ro->T % ro->bptt_len == 0, "%s: bad bptt_len", who);
+    ML_REQUIRE(ro->ld == 0 || ro->ld >= ro->N, "%s: ld %lld < N %lld", who, (long long)ro->ld,
+               (long long)ro->N);
+    ML_REQUIRE(ro->obs && ro->actions && ro->log_probs && ro->advantages &&
+                   (ro->returns || ro->values),
+               "%s: null rollout array", who);
+    ML_REQUIRE(!hp->clip_value_loss || ro->values, "%s: clip_value_loss needs values", who);
+    ML_REQUIRE(!hp->normalize_values || policy->critic_bins == 1,
+               "%s: normalize_values needs the scalar critic (ppo.py:54-57)", who);
+    return MLEARN_OK;
+}
+
 static int ppo_entry(const mlearn_mlp_policy* policy, const mlearn_rollout_view* ro,
                      const int32_t* mb_seq, int32_t mb_size, const float* adv_stats,
                      const mlearn_ppo_hparams* hp, float* grad, float* loss_out, void* workspace,
                      bool step_only, mlearn_stream_t stream) {
     int rc = validate_policy(policy);
     if (rc) return rc;
-    ML_REQUIRE(ro && mb_seq && adv_stats && hp && workspace, "ppo: null pointer");
+    rc = validate_minibatch("ppo", policy, ro, mb_seq, mb_size, adv_stats, hp, workspace);
+    if (rc) return rc;
     ML_REQUIRE(step_only || grad, "ppo: null grad");
     ML_REQUIRE(mb_size >= 1, "ppo: mb_size must be >= 1");
-    ML_REQUIRE(ro->N >= 1 && ro->N < (1ll << 31) && (int64_t)mb_size * ro->bptt_len < (1ll << 31),
-               "ppo: N and rows per minibatch must be < 2^31");
-    ML_REQUIRE(ro->bptt_len >= 1 && ro->T % ro->bptt_len == 0, "ppo: bad bptt_len");
-    ML_REQUIRE(ro->ld == 0 || ro->ld >= ro->N, "ppo: ld %lld < N %lld", (long long)ro->ld,
-               (long long)ro->N);
-    ML_REQUIRE(ro->obs && ro->actions && ro->log_probs && ro->advantages &&
-                   (ro->returns || ro->values),
-               "ppo: null rollout array");
-    ML_REQUIRE(!hp->clip_value_loss || ro->values, "ppo: clip_value_loss needs values");
-    ML_REQUIRE(!hp->normalize_values || policy->critic_bins == 1,
-               "ppo: normalize_values needs the scalar critic (ppo.py:54-57)");
     hipStream_t s = S(stream);
-#define ML_DISPATCH(T)                                                                           \
-    switch (policy->hidden) {                                                                   \
-        case 64: return launch_minibatch<T, 64>(*policy, *ro, mb_seq, mb_size, adv_stats, *hp,  \
-                                                grad, loss_out, workspace, step_only, s);       \
-        case 128: return launch_minibatch<T, 128>(*policy, *ro, mb_seq, mb_size, adv_stats, *hp, \
-                                                  grad, loss_out, workspace, step_only, s);     \
-        default: return launch_minibatch<T, 256>(*policy, *ro, mb_seq, mb_size, adv_stats, *hp, \
-                                                 grad, loss_out, workspace, step_only, s);      \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
+    return dispatch_th(policy->dtype, policy->hidden, [&](auto t, auto h) {
+        return launch_minibatch<tag_t<decltype(t)>, h>(*policy, *ro, mb_seq, mb_size, adv_stats,
+                                                       *hp, grad, loss_out, workspace, step_only, s);
+    });
 }
 
 int mlearn_ppo_minibatch_grad(const mlearn_mlp_policy* policy, const mlearn_rollout_view* ro,
@@ -1644,41 +1627,19 @@ int mlearn_lstm_ppo_minibatch_grad(const mlearn_mlp_policy* policy, const mlearn
                                    mlearn_stream_t stream) {
     int rc = validate_lstm(policy, lstm);
     if (rc) return rc;
-    ML_REQUIRE(ro && mb_seq && adv_stats && hp && workspace && grad && start_h && start_c,
-               "lstm ppo: null pointer");
+    rc = validate_minibatch("lstm ppo", policy, ro, mb_seq, mb_size, adv_stats, hp, workspace);
+    if (rc) return rc;
+    ML_REQUIRE(grad && start_h && start_c, "lstm ppo: null pointer");
     ML_REQUIRE(ro->dones, "lstm ppo: the rollout view needs dones (sequence breaks)");
     ML_REQUIRE(mb_size >= 32 && mb_size % 32 == 0, "lstm ppo: mb_size must be a multiple of 32");
     ML_REQUIRE(((int64_t)mb_size * ro->bptt_len) % 64 == 0,
                "lstm ppo: mb_size * bptt_len must be a multiple of 64");
-    ML_REQUIRE(ro->N >= 1 && ro->N < (1ll << 31) && (int64_t)mb_size * ro->bptt_len < (1ll << 31),
-               "lstm ppo: N and rows per minibatch must be < 2^31");
-    ML_REQUIRE(ro->bptt_len >= 1 && ro->T % ro->bptt_len == 0, "lstm ppo: bad bptt_len");
-    ML_REQUIRE(ro->ld == 0 || ro->ld >= ro->N, "lstm ppo: ld < N");
-    ML_REQUIRE(ro->obs && ro->actions && ro->log_probs && ro->advantages &&
-                   (ro->returns || ro->values),
-               "lstm ppo: null rollout array");
-    ML_REQUIRE(!hp->clip_value_loss || ro->values, "lstm ppo: clip_value_loss needs values");
-    ML_REQUIRE(!hp->normalize_values || policy->critic_bins == 1,
-               "lstm ppo: normalize_values needs the scalar critic (ppo.py:54-57)");
     hipStream_t s = S(stream);
-#define ML_DISPATCH(T)                                                                            \
-    switch (policy->hidden) {                                                                    \
-        case 64: return launch_minibatch_lstm<T, 64>(*policy, *lstm, *ro, start_h, start_c,      \
-                                                     mb_seq, mb_size, adv_stats, *hp, grad,      \
-                                                     loss_out, workspace, s);                    \
-        case 128: return launch_minibatch_lstm<T, 128>(*policy, *lstm, *ro, start_h, start_c,    \
-                                                       mb_seq, mb_size, adv_stats, *hp, grad,    \
-                                                       loss_out, workspace, s);                  \
-        default: return launch_minibatch_lstm<T, 256>(*policy, *lstm, *ro, start_h, start_c,     \
-                                                      mb_seq, mb_size, adv_stats, *hp, grad,     \
-                                                      loss_out, workspace, s);                   \
-    }
-    if (policy->dtype == MLEARN_DTYPE_BF16) {
-        ML_DISPATCH(bf16)
-    } else {
-        ML_DISPATCH(float)
-    }
-#undef ML_DISPATCH
+    return dispatch_th(policy->dtype, policy->hidden, [&](auto t, auto h) {
+        return launch_minibatch_lstm<tag_t<decltype(t)>, h>(*policy, *lstm, *ro, start_h, start_c,
+                                                            mb_seq, mb_size, adv_stats, *hp, grad,
+                                                            loss_out, workspace, s);
+    });
 }
 
 int mlearn_ppo_minibatch_fwd_bwd(const mlearn_mlp_policy* policy, const mlearn_rollout_view* ro,

@@ -404,8 +404,8 @@ class PolicyTrainState:
     """Optimizer + per-policy training state (train_state.py:85-136)."""
 
     # mlearn_optim_state.launch_form of the optimizer step: 0 the library's
-    # choice (the fused one-launch chain where it applies), 1 the split
-    # launches, 2 the fused launch (A/B runs; bit-identical results)
+    # choice (the split launches), 1 the split launches, 2 the fused
+    # one-launch chain where it applies (opt-in; A/B runs; bit-identical results)
     optim_launch_form = 0
 
     def __init__(self, cfg: TrainConfig, hyper_params, policy_state: PolicyState, key):

@@ -109,7 +109,11 @@ CASES = [("f32", torch.float32, 64, 256, 2), ("bf16", torch.bfloat16, 64, 256, 2
 # test_gpu_policy; appended so that the earlier cases keep their ids)
 CRITIC_CASES = [c + (1,) for c in CASES] + [
     ("f32", torch.float32, 64, 256, 2, 63), ("bf16", torch.bfloat16, 32, 64, 2, 63),
-    ("bf16", torch.bfloat16, 16, 64, 1, 1), ("bf16", torch.bfloat16, 256, 256, 4, 1)]
+    ("bf16", torch.bfloat16, 16, 64, 1, 1), ("bf16", torch.bfloat16, 256, 256, 4, 1),
+    # the remaining recurrent (dtype, hidden, head width) kernel instantiations
+    ("f32", torch.float32, 32, 128, 1, 1), ("f32", torch.float32, 32, 128, 2, 63),
+    ("f32", torch.float32, 32, 64, 1, 63), ("bf16", torch.bfloat16, 64, 256, 2, 63),
+    ("bf16", torch.bfloat16, 32, 128, 2, 63)]
 
 
 @pytest.mark.parametrize("mode,dtype,D,H,L,CB", CRITIC_CASES)

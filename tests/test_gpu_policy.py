@@ -78,7 +78,10 @@ CRITIC_CASES = [c + (1,) for c in CASES] + [
     # corners of what compile_arch admits: narrowest / widest observation, 1 and 4
     # layers, the narrowest trunk under the two-hot head
     ("bf16", torch.bfloat16, 16, 64, 1, 1), ("bf16", torch.bfloat16, 256, 256, 4, 1),
-    ("bf16", torch.bfloat16, 256, 64, 4, 63), ("f32", torch.float32, 256, 128, 4, 1)]
+    ("bf16", torch.bfloat16, 256, 64, 4, 63), ("f32", torch.float32, 256, 128, 4, 1),
+    # hidden 128 under the 96-column head: with these every feed-forward
+    # (dtype, hidden, head width) kernel instantiation is compared to the oracle
+    ("f32", torch.float32, 32, 128, 2, 63), ("bf16", torch.bfloat16, 32, 128, 2, 63)]
 
 
 @pytest.mark.parametrize("mode,dtype,D,H,L,CB", CRITIC_CASES)
