@@ -774,6 +774,40 @@ int mlearn_lstm_policy_rollout_step_env(const mlearn_mlp_policy* policy, const m
                                         uint32_t env_offset, int32_t sample,
                                         const mlearn_post_step* post, const mlearn_dummy_env* env,
                                         mlearn_stream_t stream);
+/* One rollout step with the policy chosen per env row (the reference's
+ * rollout_loop under arbitrary policy_assignments, rollouts.py:137-170,
+ * 1107-1211; evaluation and cross-play): row n runs policy assignments[n]
+ * out of a table of num_policies (1..64) feed-forward policies of one
+ * architecture -- the same dtype, obs_dim, hidden, num_layers, critic_bins
+ * and action layout; each policy's own obs_mu / obs_inv_sigma are honoured;
+ * obs_stats must be null.  The per-row arithmetic and Philox counters
+ * (env_offset + n) are those of mlearn_policy_rollout_step with that row's
+ * policy: the same bits.  Outputs in env order: actions [N][K], log_probs
+ * [N][K] (may be null when sample == 0), values [N] (may be null).  Rows with
+ * assignments[n] outside [0, num_policies) belong to no table policy: their
+ * output rows are not written.  No store write, post-step, fused env step or
+ * LSTM.
+ *   workspace: mlearn_policy_assigned_bytes(N, num_policies) device bytes
+ *     (0 for a bad argument; N <= 2^30), 16-byte aligned.
+ *   mlearn_policy_assigned_prepare copies the descriptor table to the
+ *     workspace (a copy on `stream`, complete when the call returns; call it
+ *     outside stream capture, again whenever a descriptor changes).
+ *   mlearn_policy_step_assigned (policy0 = the table's first descriptor):
+ *     two launches, capturable -- a bucket kernel that builds, per policy, the
+ *     list of its env rows (ascending, padded to whole 32-row tiles; at most
+ *     ceil(N / 32) + num_policies tiles, so the launch geometry depends on N
+ *     and num_policies only and a captured step replays after assignments
+ *     changed in place), and the policy step over those tiles.  assignments
+ *     and obs 16-byte aligned. */
+int64_t mlearn_policy_assigned_bytes(int64_t N, int32_t num_policies);
+int mlearn_policy_assigned_prepare(const mlearn_mlp_policy* policies, int32_t num_policies,
+                                   void* workspace, mlearn_stream_t stream);
+int mlearn_policy_step_assigned(const mlearn_mlp_policy* policy0, int32_t num_policies,
+                                const int32_t* assignments, const float* obs, int64_t N,
+                                int32_t* actions, float* log_probs, float* values, uint32_t k0,
+                                uint32_t k1, const uint64_t* step_ctr, uint64_t step,
+                                uint32_t env_offset, int32_t sample, void* workspace,
+                                mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
 /* Data-parallel collectives on the compute stream  */

@@ -163,6 +163,18 @@ static uint64_t* g_pol_stamp_buf = nullptr;
     } while (0)
 #endif
 
+// Env row of tile lane rr, N for none.  GATHER (mlearn_policy_step_assigned):
+// gmap[row0 + rr] for rr < glive instead of row0 + rr; every output and the
+// Philox counter keep the env index.
+template <bool GATHER>
+__device__ __forceinline__ int64_t tile_env_row(const int32_t* __restrict__ gmap, int glive,
+                                                int64_t row0, int rr, int64_t N) {
+    if constexpr (GATHER)
+        return rr < glive ? (int64_t)gmap[row0 + rr] : N;
+    else
+        return row0 + rr;
+}
+
 // RNN: the LSTM cell (RecurrentBackboneEncoder, actor_critic.py:173-177)
 // sits between the trunk and the heads.  The trunk output fragments (from
 // the accumulators, permuted k order) and the carry rows (from HBM, natural k
@@ -170,7 +182,7 @@ static uint64_t* g_pol_stamp_buf = nullptr;
 // hidden units (8 accumulator blocks, weight images in unit-block gate
 // order), so the cell update is register-local and h' lands in exactly the
 // layout the heads consume.
-template <typename T, int H, bool RNN, int HC, int MAXW, bool STAGED = false>
+template <typename T, int H, bool RNN, int HC, int MAXW, bool STAGED = false, bool GATHER = false>
 #ifndef ML_POL_WAVES
 #define ML_POL_WAVES 1  // waves per SIMD the recurrent rollout policy kernel is register-budgeted for (1: compiler choice)
 #endif
@@ -181,7 +193,8 @@ __device__ __forceinline__ void policy_step_body(
     const PolicyK& P, const float* __restrict__ obs, int64_t N, T* obs_store, int32_t* actions,
     float* logp, float* values, uint32_t k0, uint32_t k1, const uint64_t* step_ctr,
     uint64_t step_add, uint32_t eoff, int sample, const PostK& post, const LstmK& R,
-    const CarryK& cy, const EvalK& ev, const EnvK& env, int tile) {
+    const CarryK& cy, const EvalK& ev, const EnvK& env, int tile,
+    const int32_t* __restrict__ gmap = nullptr, int glive = 0) {
     typedef typename RT<T>::frag frag;
     typedef PolCfg<H, MAXW> C;
     constexpr int NBW = C::NBW, W = C::W, THREADS = 64 * W;
@@ -230,7 +243,7 @@ __device__ __forceinline__ void policy_step_body(
             for (int i = tid; i < P.CB; i += THREADS) bins[i] = twohot_bin(i, P.CB);
     }
     const int64_t row0 = (int64_t)tile * 32;
-    const int64_t row = row0 + r;
+    const int64_t row = tile_env_row<GATHER>(gmap, glive, row0, r, N);
     const bool live = row < N;
     if (post.rew && tid < 32 && row0 + tid < N) post_step_row(post, row0 + tid);
     const uint64_t step = (step_ctr ? *step_ctr : 0ull) + step_add;
@@ -472,7 +485,7 @@ __device__ __forceinline__ void policy_step_body(
             const int nq = (P.A + 3) >> 2;
             for (int task = tid; task < 32 * nq; task += THREADS) {
                 const int rr = task / nq, q = task - rr * nq;
-                const int64_t n = row0 + rr;
+                const int64_t n = tile_env_row<GATHER>(gmap, glive, row0, rr, N);
                 if (n >= N) continue;
                 const u32x4 u = philox4x32(
                     u32x4{eoff + (uint32_t)n, (uint32_t)q, (uint32_t)step, (uint32_t)(step >> 32)},
@@ -489,7 +502,7 @@ __device__ __forceinline__ void policy_step_body(
         PSTAMP(7);
         for (int task = tid; task < 32 * P.K; task += THREADS) {
             const int rr = task / P.K, g = task - rr * P.K;
-            const int64_t n = row0 + rr;
+            const int64_t n = tile_env_row<GATHER>(gmap, glive, row0, rr, N);
             if (n >= N) continue;
             int a;
             float lp;
@@ -548,7 +561,8 @@ __device__ __forceinline__ void policy_step_body(
     }
     if (values) {
         if (P.CB == 1) {
-            if (tid < 32 && row0 + tid < N) values[row0 + tid] = lg[tid * LGS + P.A];
+            if (tid < 32 && tile_env_row<GATHER>(gmap, glive, row0, tid, N) < N)
+                values[tile_env_row<GATHER>(gmap, glive, row0, tid, N)] = lg[tid * LGS + P.A];
         } else {
             // SymExpTwoHotDistribution.mean() (rollouts.py:601-605): 8 lanes per env
             constexpr int G = 8;
@@ -556,7 +570,8 @@ __device__ __forceinline__ void policy_step_body(
                 const int rr = vt / G, sub = vt % G;
                 float mx, se;
                 const float v = twohot_mean_g<G>(lg + rr * LGS + P.A, P.CB, bins, sub, &mx, &se);
-                if (sub == 0 && row0 + rr < N) values[row0 + rr] = v;
+                if (sub == 0 && tile_env_row<GATHER>(gmap, glive, row0, rr, N) < N)
+                    values[tile_env_row<GATHER>(gmap, glive, row0, rr, N)] = v;
             }
         }
     }
@@ -591,6 +606,180 @@ __global__ __launch_bounds__((pol_threads<H, RNN>())) __attribute__((amdgpu_wave
     policy_step_body<T, H, RNN, HC, pol_maxw<RNN>()>(P, obs, N, obs_store, actions, logp, values, k0, k1,
                                                  step_ctr, step_add, eoff, sample, post, R, cy, ev,
                                                  env, blockIdx.x);
+}
+
+// One rollout step with the policy chosen per env row
+// (mlearn_policy_step_assigned).  Workspace: the PolicyK table (written once
+// by mlearn_policy_assigned_prepare), then per step the tile table
+// {policy, live rows} and the row map [tiles][32] of env indices, both
+// rebuilt from `assignments` by assign_bucket_kernel.  Policy p's rows take
+// ceil(count_p / 32) consecutive tiles, in ascending env order; the tiles of
+// all policies are at most ceil(N / 32) + P, the step's grid; the bucket
+// kernel's is ceil(N / 4096).  Both are functions of N and P alone and
+// nothing on the host reads device data, so a captured step replays after
+// `assignments` changed in place.
+constexpr int kAssignMaxPolicies = 64;  // one lane per policy in the bucket kernel
+constexpr int kBktWaves = 16, kBktThreads = 64 * kBktWaves;
+constexpr int kBktSweep = 4 * kBktThreads;  // rows per sweep: one int4 per lane of a workgroup
+
+struct AssignWs {
+    PolicyK* tab;    // [P]
+    int2* tiles;     // [ntiles] {policy, live rows (0: no tile)}
+    int32_t* map;    // [ntiles][32] env index of tile lane r < live rows
+    int64_t ntiles;  // ceil(N / 32) + P
+    int64_t bytes;
+};
+
+static AssignWs assign_ws(void* ws, int64_t N, int P) {
+    auto up = [](int64_t x) { return (x + 255) / 256 * 256; };
+    AssignWs a;
+    a.ntiles = (N + 31) / 32 + P;
+    const int64_t o_tiles = up((int64_t)P * (int64_t)sizeof(PolicyK));
+    const int64_t o_map = o_tiles + up(a.ntiles * (int64_t)sizeof(int2));
+    a.bytes = o_map + up(a.ntiles * 32 * (int64_t)sizeof(int32_t));
+    a.tab = (PolicyK*)ws;
+    a.tiles = (int2*)((char*)ws + o_tiles);
+    a.map = (int32_t*)((char*)ws + o_map);
+    return a;
+}
+
+// The 4 assignments of rows i .. i + 3 (-1 past N: matches no policy).
+__device__ inline int4 load_assign4(const int32_t* __restrict__ asg, int64_t N, int64_t i) {
+    if (i + 3 < N) return *(const int4*)(asg + i);
+    return make_int4(i < N ? asg[i] : -1, i + 1 < N ? asg[i + 1] : -1, i + 2 < N ? asg[i + 2] : -1,
+                     -1);
+}
+
+// Lane p's count of policy p among the wave's 256 assignments v (0 for lanes >= P).
+__device__ inline int count_lane_policy(int4 v, int P, int lane) {
+    int c = 0;
+    for (int p = 0; p < P; ++p) {
+        const int n = __popcll(__ballot(v.x == p)) + __popcll(__ballot(v.y == p)) +
+                      __popcll(__ballot(v.z == p)) + __popcll(__ballot(v.w == p));
+        if (lane == p) c = n;
+    }
+    return c;
+}
+
+// Lanes below this one set in m.
+__device__ inline int lanes_below(unsigned long long m) {
+    return __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0));
+}
+
+// Stable partition of the env rows by assignment, integer work only.
+// Workgroup b owns the rows of sweep b, [b * 4096, (b + 1) * 4096): wave w the
+// 256 rows from w * 256 of it, lane l four consecutive ones.  Every workgroup
+// counts each policy's rows in the sweeps ahead of its own and over all N
+// (wave ballots, lane p = policy p), so it needs no other workgroup's result
+// -- ceil(N / 4096) workgroups that each read all N assignments: 16 x 256 KiB
+// at N = 65 536 -- and then ranks its own rows behind them.  Rows assigned
+// outside [0, P) match no policy: never counted, never written.  Workgroup 0
+// writes the tile table.
+__global__ __launch_bounds__(kBktThreads) void assign_bucket_kernel(
+    const int32_t* __restrict__ asg, int64_t N, int P, int2* __restrict__ tiles,
+    int32_t* __restrict__ map, int64_t ntiles) {
+    __shared__ int s_cnt[3][kBktWaves][kAssignMaxPolicies];  // sweeps ahead / own sweep / behind, per wave
+    __shared__ int s_ahead[kAssignMaxPolicies], s_total[kAssignMaxPolicies];
+    __shared__ int s_base[kAssignMaxPolicies + 1];  // first tile of policy p
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int64_t nsweep = (N + kBktSweep - 1) / kBktSweep;
+    const int64_t own = blockIdx.x;
+    const int64_t col = (int64_t)w * 256 + lane * 4;  // this lane's rows inside a sweep
+    int n_ahead = 0, n_own = 0, n_behind = 0;
+    int4 mine = make_int4(-1, -1, -1, -1);
+    constexpr int U = 8;  // loads in flight
+    for (int64_t k0 = 0; k0 < nsweep; k0 += U) {
+        int4 v[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u)
+            v[u] = load_assign4(asg, N, k0 + u < nsweep ? (k0 + u) * kBktSweep + col : N);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int64_t k = k0 + u;
+            if (k >= nsweep) break;
+            const int c = count_lane_policy(v[u], P, lane);
+            if (k < own) {
+                n_ahead += c;
+            } else if (k > own) {
+                n_behind += c;
+            } else {
+                n_own = c;
+                mine = v[u];
+            }
+        }
+    }
+    s_cnt[0][w][lane] = n_ahead;
+    s_cnt[1][w][lane] = n_own;
+    s_cnt[2][w][lane] = n_behind;
+    __syncthreads();
+    if (w == 0) {
+        int ahead = 0, total = 0;
+        for (int v = 0; v < kBktWaves; ++v) {
+            ahead += s_cnt[0][v][lane];
+            total += s_cnt[1][v][lane] + s_cnt[2][v][lane];
+        }
+        total += ahead;
+        // first tile of every policy: inclusive scan of ceil(total / 32) over the lanes
+        int incl = (total + 31) >> 5;
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(incl, o);
+            if (lane >= o) incl += t;
+        }
+        s_ahead[lane] = ahead;
+        s_total[lane] = total;
+        s_base[lane + 1] = incl;
+        if (lane == 0) s_base[0] = 0;
+    }
+    __syncthreads();
+    // rank of policy p's first row of this wave among all of p's rows (lane p):
+    // the sweeps ahead, then the waves ahead in the own sweep
+    int off = s_ahead[lane];
+    for (int v = 0; v < w; ++v) off += s_cnt[1][v][lane];
+    const int64_t row = own * kBktSweep + col;
+    for (int p = 0; p < P; ++p) {
+        const unsigned long long m0 = __ballot(mine.x == p), m1 = __ballot(mine.y == p);
+        const unsigned long long m2 = __ballot(mine.z == p), m3 = __ballot(mine.w == p);
+        if ((m0 | m1 | m2 | m3) == 0) continue;
+        // ascending env index: the lanes below (all four rows each), then this lane's rows
+        int64_t slot = (int64_t)s_base[p] * 32 + __builtin_amdgcn_readlane(off, p) +
+                       lanes_below(m0) + lanes_below(m1) + lanes_below(m2) + lanes_below(m3);
+        if (mine.x == p) map[slot++] = (int32_t)row;
+        if (mine.y == p) map[slot++] = (int32_t)(row + 1);
+        if (mine.z == p) map[slot++] = (int32_t)(row + 2);
+        if (mine.w == p) map[slot] = (int32_t)(row + 3);
+    }
+    if (blockIdx.x == 0) {
+        for (int64_t g = tid; g < ntiles; g += kBktThreads) {
+            int2 t = make_int2(0, 0);
+            for (int p = 0; p < P; ++p)
+                if (g >= s_base[p] && g < s_base[p + 1]) {
+                    const int left = s_total[p] - (int)(g - s_base[p]) * 32;
+                    t = make_int2(p, left < 32 ? left : 32);
+                }
+            tiles[g] = t;
+        }
+    }
+}
+
+// The gathered step: tile g runs policy tiles[g].x on the env rows
+// map[g * 32 + r], r < tiles[g].y, with the body and the counters of that
+// policy's own policy_step_kernel launch (the same bits per env row).
+template <typename T, int H, int HC>
+__global__ __launch_bounds__((pol_threads<H, false>())) __attribute__((amdgpu_waves_per_eu(ML_POL_MLP_WAVES, 8))) void policy_step_assigned_kernel(
+    const PolicyK* __restrict__ tab, int npol, const int2* __restrict__ tiles,
+    const int32_t* __restrict__ map, const float* __restrict__ obs, int64_t N, int32_t* actions,
+    float* logp, float* values, uint32_t k0, uint32_t k1, const uint64_t* step_ctr,
+    uint64_t step_add, uint32_t eoff, int sample) {
+    const int2 t = tiles[blockIdx.x];
+    const int p = __builtin_amdgcn_readfirstlane(t.x);
+    const int nlive = __builtin_amdgcn_readfirstlane(t.y);
+    // no rows (workgroup-uniform, ahead of every barrier); the table is never
+    // indexed outside [0, npol)
+    if (nlive <= 0 || nlive > 32 || (unsigned)p >= (unsigned)npol) return;
+    policy_step_body<T, H, false, HC, pol_maxw<false>(), false, true>(
+        tab[p], obs, N, nullptr, actions, logp, values, k0, k1, step_ctr, step_add, eoff, sample,
+        PostK{}, LstmK{}, CarryK{}, EvalK{}, EnvK{}, blockIdx.x, map, nlive);
 }
 
 // Whole rollout of the built-in synthetic sim in one launch
@@ -1284,6 +1473,111 @@ extern "C" int mlearn_lstm_policy_evaluate(const mlearn_mlp_policy* policy,
     ML_REQUIRE(actions, "lstm policy_evaluate: null actions");
     return rollout_step_entry(policy, lstm, carry, obs, N, nullptr, nullptr, log_probs, values, 0,
                               0, nullptr, 0, 0, 0, nullptr, stream, EvalK{actions, entropies});
+}
+
+// A table policy of mlearn_policy_step_assigned: a valid feed-forward
+// descriptor without the rollout's observation statistics.
+static int validate_assigned_policy(const mlearn_mlp_policy* p, const char* who) {
+    if (int rc = validate_policy(p)) return rc;
+    ML_REQUIRE(!p->obs_stats, "%s: obs_stats must be null (no observation statistics here)", who);
+    return MLEARN_OK;
+}
+
+static int validate_assigned_count(int32_t num_policies, const char* who) {
+    ML_REQUIRE(num_policies >= 1 && num_policies <= kAssignMaxPolicies,
+               "%s: num_policies must be in [1, %d] (got %d)", who, kAssignMaxPolicies,
+               num_policies);
+    return MLEARN_OK;
+}
+
+template <typename T, int H, int HC>
+static int assigned_lds_attr() {
+    return set_lds_attr((const void*)policy_step_assigned_kernel<T, H, HC>, kPolLdsLimit,
+                        "policy_step_assigned");
+}
+
+extern "C" int64_t mlearn_policy_assigned_bytes(int64_t N, int32_t num_policies) {
+    if (N < 1 || N > (int64_t)1 << 30 || num_policies < 1 || num_policies > kAssignMaxPolicies)
+        return 0;
+    return assign_ws(nullptr, N, num_policies).bytes;
+}
+
+extern "C" int mlearn_policy_assigned_prepare(const mlearn_mlp_policy* policies,
+                                              int32_t num_policies, void* workspace,
+                                              mlearn_stream_t stream) {
+    const char* who = "policy_assigned_prepare";
+    if (int rc = validate_assigned_count(num_policies, who)) return rc;
+    ML_REQUIRE(policies && workspace, "%s: null policies / workspace", who);
+    std::vector<PolicyK> h((size_t)num_policies);
+    const mlearn_mlp_policy& b = policies[0];
+    for (int p = 0; p < num_policies; ++p) {
+        const mlearn_mlp_policy& a = policies[p];
+        if (int rc = validate_assigned_policy(&a, who)) return rc;
+        ML_REQUIRE(a.dtype == b.dtype && a.obs_dim == b.obs_dim && a.hidden == b.hidden &&
+                       a.num_layers == b.num_layers && a.critic_bins == b.critic_bins,
+                   "%s: policy %d's dtype / obs_dim / hidden / num_layers / critic_bins differ "
+                   "from policy 0's", who, p);
+        bool same = a.actions.num_groups == b.actions.num_groups;
+        for (int g = 0; same && g <= b.actions.num_groups; ++g)
+            same = a.actions.offsets[g] == b.actions.offsets[g];
+        ML_REQUIRE(same, "%s: policy %d's action layout differs from policy 0's", who, p);
+        h[(size_t)p] = make_policy_k(a);
+    }
+    ML_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
+    // the kernel's LDS limit, here so that a captured step finds it set
+    if (int rc = dispatch_policy(b, nullptr, [&](auto t, auto hh, auto hc, auto) {
+            return assigned_lds_attr<tag_t<decltype(t)>, hh, hc>();
+        }))
+        return rc;
+    // ordered after the caller's earlier work on its stream (a step may still
+    // read the table), complete on return (the staging vector dies here)
+    hipError_t err = hipMemcpyAsync(workspace, h.data(), h.size() * sizeof(PolicyK),
+                                    hipMemcpyHostToDevice, S(stream));
+    if (err == hipSuccess) err = hipStreamSynchronize(S(stream));
+    if (err != hipSuccess) {
+        set_error("%s: hipMemcpy: %s", who, hipGetErrorString(err));
+        return MLEARN_EHIP;
+    }
+    return MLEARN_OK;
+}
+
+extern "C" int mlearn_policy_step_assigned(const mlearn_mlp_policy* policy0, int32_t num_policies,
+                                           const int32_t* assignments, const float* obs, int64_t N,
+                                           int32_t* actions, float* log_probs, float* values,
+                                           uint32_t k0, uint32_t k1, const uint64_t* step_ctr,
+                                           uint64_t step, uint32_t env_offset, int32_t sample,
+                                           void* workspace, mlearn_stream_t stream) {
+    const char* who = "policy_step_assigned";
+    if (int rc = validate_assigned_count(num_policies, who)) return rc;
+    if (int rc = validate_assigned_policy(policy0, who)) return rc;
+    ML_REQUIRE(assignments, "%s: null assignments", who);
+    ML_REQUIRE(N >= 0 && N <= (int64_t)1 << 30, "%s: N must be in [0, 2^30] (got %lld)", who,
+               (long long)N);
+    if (N == 0) return MLEARN_OK;
+    ML_REQUIRE(obs && actions && workspace, "%s: null obs / actions / workspace", who);
+    ML_REQUIRE(log_probs || !sample, "%s: sampling needs log_probs", who);
+    ML_REQUIRE((uintptr_t)obs % 16 == 0 && (uintptr_t)assignments % 16 == 0 &&
+                   (uintptr_t)workspace % 16 == 0,
+               "%s: obs, assignments and workspace must be 16-byte aligned", who);
+    const AssignWs ws = assign_ws(workspace, N, num_policies);
+    hipStream_t s = S(stream);
+    hipLaunchKernelGGL(assign_bucket_kernel, dim3((unsigned)((N + kBktSweep - 1) / kBktSweep)),
+                       dim3(kBktThreads), 0, s, assignments, N, (int)num_policies, ws.tiles, ws.map,
+                       ws.ntiles);
+    if (int rc = check_launch("policy_step_assigned (buckets)")) return rc;
+    const int L = policy0->num_layers;
+    return dispatch_policy(*policy0, nullptr, [&](auto t, auto hh, auto hc, auto) {
+        typedef tag_t<decltype(t)> T;
+        constexpr int H = decltype(hh)::value, HC = decltype(hc)::value;
+        if (int rc = assigned_lds_attr<T, H, HC>()) return rc;
+        const size_t lds = policy_step_lds<T, H, false, HC, pol_maxw<false>()>(L);
+        hipLaunchKernelGGL((policy_step_assigned_kernel<T, H, HC>), dim3((unsigned)ws.ntiles),
+                           dim3(pol_threads<H, false>()), lds, s, (const PolicyK*)ws.tab,
+                           (int)num_policies, (const int2*)ws.tiles, (const int32_t*)ws.map, obs, N,
+                           actions, log_probs, values, k0, k1, step_ctr, step, env_offset,
+                           (int)sample);
+        return check_launch("policy_step_assigned");
+    });
 }
 
 extern "C" int32_t mlearn_head_cols(const mlearn_mlp_policy* policy) {

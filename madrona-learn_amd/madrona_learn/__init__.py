@@ -13,6 +13,7 @@ from .actor_critic import (ActorCritic, Backbone, BackboneEncoder, BackboneSepar
 from .cfg import (ContinuousActionsConfig, DiscreteActionsConfig, EvalConfig, ParamExplore,
                   PBTConfig, TrainConfig)
 from .dists import DiscreteActionDistributions, PhiloxKey
+from .eval import eval_load_ckpt, eval_policies
 from .observations import (ObservationsCaster, ObservationsEMANormalizer,
                            ObservationsPreprocessNoop)
 from .policy import Policy
@@ -28,7 +29,7 @@ from . import rnn
 __all__ = [
     "init_training", "stop_training", "train", "TrainHooks", "TrainingManager",
     "DiscreteActionsConfig", "ContinuousActionsConfig", "TrainConfig", "PBTConfig",
-    "ParamExplore", "EvalConfig", "TrainStateManager", "models", "rnn", "Policy",
+    "ParamExplore", "EvalConfig", "eval_load_ckpt", "eval_policies", "TrainStateManager", "models", "rnn", "Policy",
     "DiscreteActionDistributions", "PhiloxKey", "ObservationsEMANormalizer",
     "ObservationsCaster", "ObservationsPreprocessNoop", "ActorCritic", "BackboneEncoder",
     "RecurrentBackboneEncoder", "Backbone", "BackboneShared", "BackboneSeparate", "PPOConfig",

@@ -177,6 +177,11 @@ _SIGNATURES = {
                                                 c_int64, c_uint32, c_uint32, _P, c_int32, _S]),
     "mlearn_policy_rollout_pop_workgroups": (c_int64, [POINTER(MlpPolicy), POINTER(Lstm),
                                                        c_int64, c_int32, c_int32]),
+    "mlearn_policy_assigned_bytes": (c_int64, [c_int64, c_int32]),
+    "mlearn_policy_assigned_prepare": (c_int32, [POINTER(MlpPolicy), c_int32, _P, _S]),
+    "mlearn_policy_step_assigned": (c_int32, [POINTER(MlpPolicy), c_int32, _P, _P, c_int64, _P,
+                                              _P, _P, c_uint32, c_uint32, _P, c_uint64, c_uint32,
+                                              c_int32, _P, _S]),
     "mlearn_policy_evaluate": (c_int32, [POINTER(MlpPolicy), _P, c_int64, _P, _P, _P, _P, _S]),
     "mlearn_lstm_policy_evaluate": (c_int32, [POINTER(MlpPolicy), POINTER(Lstm), POINTER(LstmCarry),
                                               _P, c_int64, _P, _P, _P, _P, _S]),

@@ -147,7 +147,7 @@ class TrainConfig:  # cfg.py:68-127
 
 
 @dataclass(frozen=True)
-class EvalConfig:  # cfg.py:130-142 (eval is outside the accelerated path)
+class EvalConfig:  # cfg.py:130-142 (consumed by eval.eval_policies)
     num_worlds: int
     num_teams: int
     team_size: int

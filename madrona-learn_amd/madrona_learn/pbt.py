@@ -11,6 +11,9 @@ and the initial hyperparameter draw of train.py:320-351).
   (ppo.py:231-239): exploration changes the recorded hyperparameters.
 * ``pbt_update_fitness`` (pbt.py:382-470): per policy EMA (decay 0.9999) of
   the scores of the episodes that ended this step.
+* ``pbt_update_elo`` (pbt.py:258-343): Elo ratings of the policies of a
+  two-team match-up from the matches that ended this step (K = 1), used by
+  ``eval.eval_policies``' competitive evaluation.
 * ``pbt_cull_update`` (pbt.py:609-682): the ``num_cull_policies`` least fit
   train policies take the state of the most fit ones when the one-sided test
   of _check_overwrite (pbt.py:565-600) passes, keeping their own minibatch
@@ -208,6 +211,54 @@ def pbt_update_fitness(policy_columns, episode_scores, dones, team_size=1):
         sc.mean.copy_(torch.where(upd, cw * sc.mean + xw * xm, sc.mean))
         sc.var.copy_(torch.where(upd, cw * sc.var + xw * xv + mdv, sc.var))
         sc.N.copy_(torch.where(upd, new_n, sc.N))
+
+
+def elo_expected_result(my_elo, opponent_elo):  # pbt.py:258-262
+    return 1.0 / (1.0 + 10.0 ** ((opponent_elo - my_elo) / 400.0))
+
+
+def pbt_update_elo(get_episode_scores, assignments, dones, episode_results, elos, num_teams,
+                   team_size, custom_policy_ids=()):
+    """pbt.py:264-343 as device tensor ops: the Elo ratings after this step's
+    finished matches.  ``assignments`` / ``dones`` per agent ([matches *
+    num_teams * team_size]); agent 0 of team A decides ``done`` and each team
+    plays the policy of its agent 0.  ``elos`` f32 [table policies + custom
+    ids]: custom id i takes slot ``len(elos) - len(custom_policy_ids) + i``.
+    ``get_episode_scores(episode_results)`` returns (a_scores, b_scores) per
+    match.  A match of one policy against itself is skipped; K = 1: every
+    policy moves by the sum over its matches of score - expected score, all
+    expectations from the ratings before the step.  Returns the new ratings
+    (``elos`` is not written)."""
+    if int(num_teams) != 2:
+        raise ValueError("pbt_update_elo: two teams (pbt.py:281)")
+    a = assignments.reshape(-1).to(torch.int64)
+    num_slots = elos.numel()
+    first_custom = num_slots - len(custom_policy_ids)
+    for i, cid in enumerate(custom_policy_ids):  # _convert_custom_policy_ids
+        a = torch.where(a == int(cid), first_custom + i, a)
+    a = a.reshape(-1, 2, int(team_size))
+    a_pol, b_pol = a[:, 0, 0], a[:, 1, 0]
+    done = dones.reshape(-1, 2, int(team_size))[:, 0, 0].bool()
+    a_score, b_score = get_episode_scores(episode_results)
+    # ratings are kept in float32 like the reference's; the step itself runs in
+    # float64 and rounds once, so the result does not depend on the order of
+    # the sum (a float32 rating near 1500 resolves 1.2e-4)
+    a_score = a_score.reshape(-1).to(torch.float64)
+    b_score = b_score.reshape(-1).to(torch.float64)
+    e = elos.reshape(-1).to(torch.float64)
+    in_range = (a_pol >= 0) & (a_pol < num_slots) & (b_pol >= 0) & (b_pol < num_slots)
+    valid = done & (a_pol != b_pol) & in_range
+    ai = a_pol.clamp(0, num_slots - 1)
+    bi = b_pol.clamp(0, num_slots - 1)
+    a_elo, b_elo = e[ai], e[bi]
+    zero = torch.zeros_like(a_score)
+    a_diff = torch.where(valid, a_score - elo_expected_result(a_elo, b_elo), zero)
+    b_diff = torch.where(valid, b_score - elo_expected_result(b_elo, a_elo), zero)
+    # per policy, the sum over the matches it played on either side
+    slots = torch.arange(num_slots, device=e.device)[:, None]
+    diffs = torch.where(ai[None, :] == slots, a_diff[None, :], zero[None, :]) + \
+        torch.where(bi[None, :] == slots, b_diff[None, :], zero[None, :])
+    return (e + diffs.sum(dim=1)).to(torch.float32)
 
 
 def check_overwrite(cfg, mean, var, N, src, dst):

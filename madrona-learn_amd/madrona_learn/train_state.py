@@ -8,6 +8,7 @@ kernels read, all bound into one ``mlearn_mlp_policy`` descriptor.
 weight norms (train_state.py:413-423) and the minibatch RNG key.
 """
 
+import ctypes
 import math
 from dataclasses import dataclass, field
 from typing import Any, Optional
@@ -398,6 +399,66 @@ class PolicyState:
             nat.ptr(self.obs_stats), self.obs_stats.shape[0], self.obs_stats.shape[1],
             self._obs_B, self.arch.obs_dim, float(n.decay), float(n.eps), nat.ptr(self.obs_est),
             nat.ptr(self.obs_count), nat.stream_handle()), "obs_norm_update")
+
+
+class AssignedPolicyStep:
+    """One rollout step with the policy chosen per env row
+    (mlearn_policy_step_assigned): row n runs ``policy_states[assignments[n]]``;
+    rows assigned outside the table (the reference's custom policy ids,
+    rollouts.py:137-170) are left unwritten.  Feed-forward policies of one
+    architecture.  Holds the workspace and the device descriptor table; call
+    ``prepare`` again after a policy's buffers were replaced."""
+
+    def __init__(self, policy_states, N):
+        self.policies = list(policy_states)
+        if not self.policies:
+            raise ValueError("AssignedPolicyStep: no policies")
+        arch = self.policies[0].arch
+        for ps in self.policies:
+            if ps.recurrent:
+                raise NotImplementedError("mixed policy assignment: feed-forward policies only "
+                                          "(no recurrent carry per assignment)")
+            if ps.arch != arch:
+                raise ValueError("mixed policy assignment: the policies must share one "
+                                 "architecture")
+        self.N = int(N)
+        self.P = len(self.policies)
+        nbytes = int(nat.lib().mlearn_policy_assigned_bytes(self.N, self.P))
+        if nbytes <= 0:
+            raise ValueError(f"mixed policy assignment: bad shape (N={self.N}, "
+                             f"{self.P} policies)")
+        self.workspace = torch.zeros(nbytes, dtype=torch.uint8, device=self.policies[0].device)
+        self.prepare()
+
+    def prepare(self):
+        """Copy the descriptor table to the device (outside graph capture)."""
+        descs = (nat.MlpPolicy * self.P)()
+        for i, ps in enumerate(self.policies):
+            # a copy of the policy's descriptor without the rollout's
+            # observation statistics buffer
+            ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(ps.desc),
+                           ctypes.sizeof(nat.MlpPolicy))
+            descs[i].obs_stats = None
+            descs[i].obs_stats_tiles = 0
+            descs[i].obs_stats_steps = 0
+        self.descs = descs
+        nat.check(nat.lib().mlearn_policy_assigned_prepare(
+            descs, self.P, nat.ptr(self.workspace), nat.stream_handle()),
+            "policy_assigned_prepare")
+
+    def step(self, assignments, obs, actions, log_probs, values, key, step_ctr, step,
+             env_offset=0, sample=True):
+        """assignments: int32 [N] (or [N, 1]) device tensor, read by the launch
+        (it may change in place between replays of a captured step)."""
+        N = obs.shape[0]
+        if N != self.N:
+            raise ValueError(f"AssignedPolicyStep built for {self.N} rows, got {N}")
+        nat.check(nat.lib().mlearn_policy_step_assigned(
+            self.descs, self.P, nat.ptr(assignments, torch.int32, N, "assignments"),
+            nat.ptr(obs, torch.float32, name="obs"), N, nat.ptr(actions, torch.int32),
+            nat.ptr(log_probs), nat.ptr(values), key[0], key[1], nat.ptr(step_ctr), step,
+            env_offset, 1 if sample else 0, nat.ptr(self.workspace), nat.stream_handle()),
+            "policy_step_assigned")
 
 
 class PolicyTrainState:
