@@ -809,6 +809,59 @@ int mlearn_policy_step_assigned(const mlearn_mlp_policy* policy0, int32_t num_po
                                 uint32_t env_offset, int32_t sample, void* workspace,
                                 mlearn_stream_t stream);
 
+/* The matched rollout step: mlearn_policy_step_assigned extended into a full
+ * rollout step of league training (cross-play / past-play matchmaking,
+ * rollouts.py:579-714, 944-973).  Same bucket kernel, workspace and prepared
+ * table (mlearn_policy_assigned_prepare; train policies then past slots).
+ * Sim row n runs policy assignments[n]; train_col[n] is its column in the
+ * train store ([num_train_cols] leading dimension), or -1 (any value outside
+ * [0, num_train_cols)) for an opponent row, which stores nothing.  Per-row
+ * arithmetic and Philox counters (env_offset + n) are those of
+ * mlearn_policy_rollout_step with that row's policy: the same bits.
+ *   store rows of step t, in train space: obs_store [cols][obs_dim] (compute
+ *     dtype, may be null), store_actions [cols][K], store_log_probs [cols][K],
+ *     store_values [cols].
+ *   actions [N][K], sim order: written for every row of a table policy.
+ *   post (may be null): the post-step of the previous env step; rewards,
+ *     dones and env_returns in sim order [N] (env_returns updated and zeroed
+ *     where done for all N rows), store_rewards, store_dones and
+ *     env_returns_trace in train space, written through train_col.
+ *   actions == NULL: critic only; store_values is then the bootstrap row
+ *     [cols], obs_store / store_actions / store_log_probs must be null.
+ * Rows assigned outside the table write nothing.  Two launches, capturable;
+ * a captured step replays after assignments changed in place. */
+int mlearn_policy_rollout_step_matched(const mlearn_mlp_policy* policy0, int32_t num_policies,
+                                       const int32_t* assignments, const int32_t* train_col,
+                                       int64_t num_train_cols, const float* obs, int64_t N,
+                                       void* obs_store, int32_t* store_actions,
+                                       float* store_log_probs, float* store_values,
+                                       int32_t* actions, uint32_t k0, uint32_t k1,
+                                       const uint64_t* step_ctr, uint64_t step,
+                                       uint32_t env_offset, int32_t sample,
+                                       const mlearn_post_step* post, void* workspace,
+                                       mlearn_stream_t stream);
+
+/* pbt_update_matchmaking (pbt.py:210-255, 346-379) in place on the device,
+ * one launch whose geometry depends on cfg alone.  Sim rows are [self | cross
+ * | past], each region matches of num_teams x team_size agents; team 0 of a
+ * match keeps the match's base policy.  An agent of team k >= 1 with dones set
+ * takes the draw of its (match m of the region, team k): d = mulhi(word 0 of
+ * Philox4x32-10 counter {step lo, step hi, m, region << 16 | k}, n), step =
+ * *step_ctr (0 when null) + step; cross play (region 1): n = P - 1, opponent
+ * d + (d >= base); past play (region 2): n = Q, opponent P + d. */
+typedef struct mlearn_matchmake_cfg {
+    int64_t self_play_batch_size;
+    int64_t cross_play_batch_size;
+    int64_t past_play_batch_size;
+    int32_t num_current_policies;  /* P */
+    int32_t num_past_policies;     /* Q */
+    int32_t num_teams;
+    int32_t team_size;
+} mlearn_matchmake_cfg;
+int mlearn_matchmake_update(int32_t* assignments, const uint8_t* dones,
+                            const mlearn_matchmake_cfg* cfg, uint32_t k0, uint32_t k1,
+                            const uint64_t* step_ctr, uint64_t step, mlearn_stream_t stream);
+
 /* ---------------------------------------------------------------------- */
 /* Data-parallel collectives on the compute stream  */
 /* ---------------------------------------------------------------------- */

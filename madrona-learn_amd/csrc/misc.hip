@@ -628,6 +628,50 @@ __global__ __launch_bounds__(256) void post_step_kernel(const float* __restrict_
 }
 
 // ---------------------------------------------------------------------------
+// Matchmaking update (pbt.py:210-255, 346-379).
+// ---------------------------------------------------------------------------
+// One lane per agent row of the cross-play and past-play regions (the sim
+// rows are [self | cross | past], each region matches of teams x team_size
+// agents).  An agent of team k >= 1 whose done is set takes the draw of its
+// (match, team): mulhi(word 0 of Philox {step lo, step hi, match, region <<
+// 16 | k}, n); team 0 (whose agent 0 names the match's base policy) and the
+// self-play region are never written, so no lane reads a row another writes.
+struct MatchmakeK {
+    int64_t cross0, past0, end;  // first row of the cross / past region, one past the last row
+    int P, Q, teams, team_size;
+};
+
+__global__ __launch_bounds__(256) void matchmake_update_kernel(int32_t* asg,
+                                                               const uint8_t* __restrict__ done,
+                                                               MatchmakeK c, uint32_t k0,
+                                                               uint32_t k1,
+                                                               const uint64_t* step_ctr,
+                                                               uint64_t step_add) {
+    const int64_t row = c.cross0 + blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+    if (row >= c.end) return;
+    const bool past = row >= c.past0;
+    const int64_t r0 = past ? c.past0 : c.cross0;
+    const int64_t apw = (int64_t)c.teams * c.team_size;
+    const int64_t m = (row - r0) / apw;
+    const int k = (int)((row - r0 - m * apw) / c.team_size);
+    if (k == 0 || done[row] == 0) return;
+    const uint64_t step = (step_ctr ? *step_ctr : 0ull) + step_add;
+    const uint32_t region = past ? 2u : 1u;
+    const u32x4 w = philox4x32(u32x4{(uint32_t)step, (uint32_t)(step >> 32), (uint32_t)m,
+                                     (region << 16) | (uint32_t)k},
+                               k0, k1);
+    const uint32_t n = past ? (uint32_t)c.Q : (uint32_t)(c.P - 1);
+    int32_t d = (int32_t)__umulhi(w.x, n);
+    if (past) {
+        d += c.P;
+    } else {
+        const int32_t base = asg[r0 + m * apw];
+        if (d >= base) d += 1;
+    }
+    asg[row] = d;
+}
+
+// ---------------------------------------------------------------------------
 // Synthetic dummy vec-env (bench/test sim plugin).
 // ---------------------------------------------------------------------------
 // state[n] = {episode step, env step lo, env step hi, 0}.  A workgroup owns
@@ -1116,6 +1160,34 @@ int mlearn_adv_stats_finish(const double* partials, int32_t num_mb, double count
     hipLaunchKernelGGL(adv_stats_finish_kernel, dim3((num_mb + 63) / 64), dim3(64), 0, S(stream),
                        partials, num_mb, count, stats);
     return check_launch("adv_stats_finish");
+}
+
+int mlearn_matchmake_update(int32_t* assignments, const uint8_t* dones,
+                            const mlearn_matchmake_cfg* cfg, uint32_t k0, uint32_t k1,
+                            const uint64_t* step_ctr, uint64_t step, mlearn_stream_t stream) {
+    ML_REQUIRE(cfg, "matchmake_update: null cfg");
+    const int64_t sb = cfg->self_play_batch_size, cb = cfg->cross_play_batch_size;
+    const int64_t pb = cfg->past_play_batch_size;
+    ML_REQUIRE(sb >= 0 && cb >= 0 && pb >= 0 && sb + cb + pb <= (int64_t)1 << 30,
+               "matchmake_update: batch sizes must be >= 0 and sum to <= 2^30");
+    ML_REQUIRE(cfg->num_teams >= 1 && cfg->num_teams <= 0xFFFF && cfg->team_size >= 1,
+               "matchmake_update: num_teams in [1, 65535], team_size >= 1");
+    const int64_t apw = (int64_t)cfg->num_teams * cfg->team_size;
+    ML_REQUIRE(cb % apw == 0 && pb % apw == 0,
+               "matchmake_update: the cross / past batch must hold whole matches");
+    ML_REQUIRE(cfg->num_current_policies >= 1 && cfg->num_past_policies >= 0,
+               "matchmake_update: bad policy counts");
+    ML_REQUIRE(cb == 0 || cfg->num_current_policies >= 2,
+               "matchmake_update: cross play needs >= 2 train policies");
+    ML_REQUIRE(pb == 0 || cfg->num_past_policies >= 1,
+               "matchmake_update: past play needs >= 1 past policy");
+    if (cb + pb == 0) return MLEARN_OK;
+    ML_REQUIRE(assignments && dones, "matchmake_update: null pointer");
+    const MatchmakeK c{sb, sb + cb, sb + cb + pb, cfg->num_current_policies,
+                       cfg->num_past_policies, cfg->num_teams, cfg->team_size};
+    hipLaunchKernelGGL(matchmake_update_kernel, dim3((unsigned)((cb + pb + 255) / 256)),
+                       dim3(256), 0, S(stream), assignments, dones, c, k0, k1, step_ctr, step);
+    return check_launch("matchmake_update");
 }
 
 int mlearn_rollout_post_step(const float* rewards, const uint8_t* dones, int64_t N,

@@ -101,6 +101,47 @@ __device__ inline void post_step_row(const PostK& p, int64_t n) {
     p.env_ret[n] = d ? 0.f : er;
 }
 
+// Train-space outputs of the matched step (mlearn_policy_rollout_step_matched):
+// sim row n stores to column tcol[n] of the [ncol]-wide train store, rows with
+// tcol[n] outside [0, ncol) (opponents) store nothing.
+struct MatchK {
+    const int32_t* tcol;  // [N]
+    int32_t* sact;        // [ncol][K] store actions (the sim-order actions are the body's `actions`)
+    int64_t ncol;
+};
+
+__device__ __forceinline__ int64_t match_col(const MatchK& mk, int64_t n) {
+    const int32_t c = mk.tcol[n];
+    return (uint64_t)(int64_t)c < (uint64_t)mk.ncol ? (int64_t)c : -1;
+}
+
+// Where env row `row` stores its observation: its own row of the step's store,
+// or (MATCHED) its column of the train store, if it has one.
+template <bool MATCHED, typename T>
+__device__ __forceinline__ T* obs_store_row(T* obs_store, int64_t row, int D, const MatchK* mkp) {
+    if constexpr (MATCHED) {
+        const int64_t c = match_col(*mkp, row);
+        return c >= 0 ? obs_store + c * D : nullptr;
+    } else {
+        return obs_store + row * D;
+    }
+}
+
+// post_step_row with the store writes through tcol; env_returns for every row.
+__device__ inline void post_step_row_matched(const PostK& p, const MatchK& mk, int64_t n) {
+#pragma clang fp contract(off)
+    const float r = p.rew[n];
+    const uint8_t d = p.done[n] ? 1 : 0;
+    const float er = r + p.gamma * p.env_ret[n];
+    const int64_t c = match_col(mk, n);
+    if (c >= 0) {
+        if (p.trace) p.trace[c] = er;
+        p.srew[c] = r;
+        p.sdone[c] = d;
+    }
+    p.env_ret[n] = d ? 0.f : er;
+}
+
 // One workgroup = 32 environments (one per lane pair); its W waves split the
 // hidden features (wave w owns blocks w*NBW .. w*NBW+NBW-1 of every layer).
 // Per layer: each wave's MFMAs over the full input (B fragments from LDS),
@@ -182,7 +223,8 @@ __device__ __forceinline__ int64_t tile_env_row(const int32_t* __restrict__ gmap
 // hidden units (8 accumulator blocks, weight images in unit-block gate
 // order), so the cell update is register-local and h' lands in exactly the
 // layout the heads consume.
-template <typename T, int H, bool RNN, int HC, int MAXW, bool STAGED = false, bool GATHER = false>
+template <typename T, int H, bool RNN, int HC, int MAXW, bool STAGED = false, bool GATHER = false,
+          bool MATCHED = false>
 #ifndef ML_POL_WAVES
 #define ML_POL_WAVES 1  // waves per SIMD the recurrent rollout policy kernel is register-budgeted for (1: compiler choice)
 #endif
@@ -194,7 +236,7 @@ __device__ __forceinline__ void policy_step_body(
     float* logp, float* values, uint32_t k0, uint32_t k1, const uint64_t* step_ctr,
     uint64_t step_add, uint32_t eoff, int sample, const PostK& post, const LstmK& R,
     const CarryK& cy, const EvalK& ev, const EnvK& env, int tile,
-    const int32_t* __restrict__ gmap = nullptr, int glive = 0) {
+    const int32_t* __restrict__ gmap = nullptr, int glive = 0, const MatchK* mkp = nullptr) {
     typedef typename RT<T>::frag frag;
     typedef PolCfg<H, MAXW> C;
     constexpr int NBW = C::NBW, W = C::W, THREADS = 64 * W;
@@ -269,8 +311,9 @@ __device__ __forceinline__ void policy_step_body(
     zero_acc<NBW>(acc);
     gemm_first<T, NBW>(acc, obs + (live ? row : 0) * D, live, D / KS,
                        (const T*)P.wt[0] + (int64_t)w * NBW * (D / KS) * 64 * E,
-                       (w == 0 && obs_store && live) ? obs_store + row * D : nullptr, lane,
-                       P.obs_mu, P.obs_inv);
+                       (w == 0 && obs_store && live) ? obs_store_row<MATCHED>(obs_store, row, D, mkp)
+                                                     : nullptr,
+                       lane, P.obs_mu, P.obs_inv);
     PSTAMP(1);
     if constexpr (!STAGED) {
 #pragma unroll
@@ -509,7 +552,15 @@ __device__ __forceinline__ void policy_step_body(
             pick_group(lg + rr * LGS + P.off[g], sample ? nz + rr * LGS + P.off[g] : nullptr,
                        P.off[g + 1] - P.off[g], &a, &lp);
             actions[n * P.K + g] = a;
-            if (logp) logp[n * P.K + g] = lp;
+            if constexpr (MATCHED) {
+                const int64_t c = match_col(*mkp, n);
+                if (c >= 0) {
+                    mkp->sact[c * P.K + g] = a;
+                    if (logp) logp[c * P.K + g] = lp;
+                }
+            } else {
+                if (logp) logp[n * P.K + g] = lp;
+            }
             // fused env: reward, done and state advance of env n from its first
             // action (every lane's state read above is behind the heads' barrier)
             if (fenv && g == 0) {
@@ -559,7 +610,27 @@ __device__ __forceinline__ void policy_step_body(
             }
         }
     }
-    if (values) {
+    if constexpr (MATCHED) {
+        if (values) {
+            if (P.CB == 1) {
+                if (tid < 32 && tid < glive) {
+                    const int64_t c = match_col(*mkp, (int64_t)gmap[row0 + tid]);
+                    if (c >= 0) values[c] = lg[tid * LGS + P.A];
+                }
+            } else {
+                constexpr int G = 8;
+                for (int vt = tid; vt < 32 * G; vt += THREADS) {
+                    const int rr = vt / G, sub = vt % G;
+                    float mx, se;
+                    const float v = twohot_mean_g<G>(lg + rr * LGS + P.A, P.CB, bins, sub, &mx, &se);
+                    if (sub == 0 && rr < glive) {
+                        const int64_t c = match_col(*mkp, (int64_t)gmap[row0 + rr]);
+                        if (c >= 0) values[c] = v;
+                    }
+                }
+            }
+        }
+    } else if (values) {
         if (P.CB == 1) {
             if (tid < 32 && tile_env_row<GATHER>(gmap, glive, row0, tid, N) < N)
                 values[tile_env_row<GATHER>(gmap, glive, row0, tid, N)] = lg[tid * LGS + P.A];
@@ -780,6 +851,32 @@ __global__ __launch_bounds__((pol_threads<H, false>())) __attribute__((amdgpu_wa
     policy_step_body<T, H, false, HC, pol_maxw<false>(), false, true>(
         tab[p], obs, N, nullptr, actions, logp, values, k0, k1, step_ctr, step_add, eoff, sample,
         PostK{}, LstmK{}, CarryK{}, EvalK{}, EnvK{}, blockIdx.x, map, nlive);
+}
+
+// The gathered step as a full rollout step (mlearn_policy_rollout_step_matched):
+// the same tiles and body; the store rows go through mk.tcol into the train
+// store, the sim-order actions are written for every row of a table policy.
+// The post-step of the previous env step runs over the sim rows in launch
+// order (workgroup b: rows [32 b, 32 b + 32); the grid has at least ceil(N /
+// 32) workgroups), ahead of the tile's own early exit: the body reads nothing
+// the post-step writes.
+template <typename T, int H, int HC>
+__global__ __launch_bounds__((pol_threads<H, false>())) __attribute__((amdgpu_waves_per_eu(ML_POL_MLP_WAVES, 8))) void policy_step_matched_kernel(
+    const PolicyK* __restrict__ tab, int npol, const int2* __restrict__ tiles,
+    const int32_t* __restrict__ map, const float* __restrict__ obs, int64_t N, T* obs_store,
+    int32_t* actions, float* logp, float* values, uint32_t k0, uint32_t k1,
+    const uint64_t* step_ctr, uint64_t step_add, uint32_t eoff, int sample, PostK post, MatchK mk) {
+    if (post.rew && threadIdx.x < 32) {
+        const int64_t n = (int64_t)blockIdx.x * 32 + threadIdx.x;
+        if (n < N) post_step_row_matched(post, mk, n);
+    }
+    const int2 t = tiles[blockIdx.x];
+    const int p = __builtin_amdgcn_readfirstlane(t.x);
+    const int nlive = __builtin_amdgcn_readfirstlane(t.y);
+    if (nlive <= 0 || nlive > 32 || (unsigned)p >= (unsigned)npol) return;
+    policy_step_body<T, H, false, HC, pol_maxw<false>(), false, true, true>(
+        tab[p], obs, N, obs_store, actions, logp, values, k0, k1, step_ctr, step_add, eoff, sample,
+        PostK{}, LstmK{}, CarryK{}, EvalK{}, EnvK{}, blockIdx.x, map, nlive, &mk);
 }
 
 // Whole rollout of the built-in synthetic sim in one launch
@@ -1496,6 +1593,12 @@ static int assigned_lds_attr() {
                         "policy_step_assigned");
 }
 
+template <typename T, int H, int HC>
+static int matched_lds_attr() {
+    return set_lds_attr((const void*)policy_step_matched_kernel<T, H, HC>, kPolLdsLimit,
+                        "policy_rollout_step_matched");
+}
+
 extern "C" int64_t mlearn_policy_assigned_bytes(int64_t N, int32_t num_policies) {
     if (N < 1 || N > (int64_t)1 << 30 || num_policies < 1 || num_policies > kAssignMaxPolicies)
         return 0;
@@ -1526,7 +1629,8 @@ extern "C" int mlearn_policy_assigned_prepare(const mlearn_mlp_policy* policies,
     ML_REQUIRE((uintptr_t)workspace % 16 == 0, "%s: workspace must be 16-byte aligned", who);
     // the kernel's LDS limit, here so that a captured step finds it set
     if (int rc = dispatch_policy(b, nullptr, [&](auto t, auto hh, auto hc, auto) {
-            return assigned_lds_attr<tag_t<decltype(t)>, hh, hc>();
+            if (int rc = assigned_lds_attr<tag_t<decltype(t)>, hh, hc>()) return rc;
+            return matched_lds_attr<tag_t<decltype(t)>, hh, hc>();
         }))
         return rc;
     // ordered after the caller's earlier work on its stream (a step may still
@@ -1577,6 +1681,61 @@ extern "C" int mlearn_policy_step_assigned(const mlearn_mlp_policy* policy0, int
                            actions, log_probs, values, k0, k1, step_ctr, step, env_offset,
                            (int)sample);
         return check_launch("policy_step_assigned");
+    });
+}
+
+extern "C" int mlearn_policy_rollout_step_matched(
+    const mlearn_mlp_policy* policy0, int32_t num_policies, const int32_t* assignments,
+    const int32_t* train_col, int64_t num_train_cols, const float* obs, int64_t N,
+    void* obs_store, int32_t* store_actions, float* store_log_probs, float* store_values,
+    int32_t* actions, uint32_t k0, uint32_t k1, const uint64_t* step_ctr, uint64_t step,
+    uint32_t env_offset, int32_t sample, const mlearn_post_step* post, void* workspace,
+    mlearn_stream_t stream) {
+    const char* who = "policy_rollout_step_matched";
+    if (int rc = validate_assigned_count(num_policies, who)) return rc;
+    if (int rc = validate_assigned_policy(policy0, who)) return rc;
+    ML_REQUIRE(assignments && train_col, "%s: null assignments / train_col", who);
+    ML_REQUIRE(N >= 0 && N <= (int64_t)1 << 30, "%s: N must be in [0, 2^30] (got %lld)", who,
+               (long long)N);
+    ML_REQUIRE(num_train_cols >= 0 && num_train_cols <= N,
+               "%s: num_train_cols must be in [0, N] (got %lld)", who, (long long)num_train_cols);
+    if (N == 0) return MLEARN_OK;
+    ML_REQUIRE(obs && workspace, "%s: null obs / workspace", who);
+    ML_REQUIRE(store_values, "%s: null store_values (the bootstrap row when actions is null)", who);
+    ML_REQUIRE(!actions || (store_actions && (store_log_probs || !sample)),
+               "%s: an acting step needs store_actions, and store_log_probs when sampling", who);
+    ML_REQUIRE(actions || (!obs_store && !store_actions && !store_log_probs),
+               "%s: the critic-only call (actions null) writes store_values only", who);
+    ML_REQUIRE((uintptr_t)obs % 16 == 0 && (uintptr_t)assignments % 16 == 0 &&
+                   (uintptr_t)workspace % 16 == 0 && (!obs_store || (uintptr_t)obs_store % 16 == 0),
+               "%s: obs, assignments, workspace and obs_store must be 16-byte aligned", who);
+    PostK pk{};
+    if (post) {
+        ML_REQUIRE(post->rewards && post->dones && post->store_rewards && post->store_dones &&
+                       post->env_returns,
+                   "%s: null post-step pointer", who);
+        pk = PostK{post->rewards, post->dones, post->store_rewards, post->store_dones,
+                   post->env_returns, post->env_returns_trace, post->gamma};
+    }
+    const MatchK mk{train_col, store_actions, num_train_cols};
+    const AssignWs ws = assign_ws(workspace, N, num_policies);
+    hipStream_t s = S(stream);
+    hipLaunchKernelGGL(assign_bucket_kernel, dim3((unsigned)((N + kBktSweep - 1) / kBktSweep)),
+                       dim3(kBktThreads), 0, s, assignments, N, (int)num_policies, ws.tiles, ws.map,
+                       ws.ntiles);
+    if (int rc = check_launch("policy_rollout_step_matched (buckets)")) return rc;
+    const int L = policy0->num_layers;
+    return dispatch_policy(*policy0, nullptr, [&](auto t, auto hh, auto hc, auto) {
+        typedef tag_t<decltype(t)> T;
+        constexpr int H = decltype(hh)::value, HC = decltype(hc)::value;
+        if (int rc = matched_lds_attr<T, H, HC>()) return rc;
+        const size_t lds = policy_step_lds<T, H, false, HC, pol_maxw<false>()>(L);
+        hipLaunchKernelGGL((policy_step_matched_kernel<T, H, HC>), dim3((unsigned)ws.ntiles),
+                           dim3(pol_threads<H, false>()), lds, s, (const PolicyK*)ws.tab,
+                           (int)num_policies, (const int2*)ws.tiles, (const int32_t*)ws.map, obs, N,
+                           (T*)obs_store, actions, store_log_probs, store_values, k0, k1, step_ctr,
+                           step, env_offset, (int)sample, pk, mk);
+        return check_launch("policy_rollout_step_matched");
     });
 }
 

@@ -120,6 +120,12 @@ class RolloutOut(Structure):  # mlearn_rollout_out
                 ("advantages", c_void_p), ("gae_gamma", c_float), ("gae_gamma_lambda", c_float)]
 
 
+class MatchmakeCfg(Structure):  # mlearn_matchmake_cfg
+    _fields_ = [("self_play_batch_size", c_int64), ("cross_play_batch_size", c_int64),
+                ("past_play_batch_size", c_int64), ("num_current_policies", c_int32),
+                ("num_past_policies", c_int32), ("num_teams", c_int32), ("team_size", c_int32)]
+
+
 _S = c_void_p  # hipStream_t
 _P = c_void_p
 
@@ -182,6 +188,12 @@ _SIGNATURES = {
     "mlearn_policy_step_assigned": (c_int32, [POINTER(MlpPolicy), c_int32, _P, _P, c_int64, _P,
                                               _P, _P, c_uint32, c_uint32, _P, c_uint64, c_uint32,
                                               c_int32, _P, _S]),
+    "mlearn_policy_rollout_step_matched": (c_int32, [POINTER(MlpPolicy), c_int32, _P, _P, c_int64,
+                                                     _P, c_int64, _P, _P, _P, _P, _P, c_uint32,
+                                                     c_uint32, _P, c_uint64, c_uint32, c_int32,
+                                                     POINTER(PostStep), _P, _S]),
+    "mlearn_matchmake_update": (c_int32, [_P, _P, POINTER(MatchmakeCfg), c_uint32, c_uint32, _P,
+                                          c_uint64, _S]),
     "mlearn_policy_evaluate": (c_int32, [POINTER(MlpPolicy), _P, c_int64, _P, _P, _P, _P, _S]),
     "mlearn_lstm_policy_evaluate": (c_int32, [POINTER(MlpPolicy), POINTER(Lstm), POINTER(LstmCarry),
                                               _P, c_int64, _P, _P, _P, _P, _S]),

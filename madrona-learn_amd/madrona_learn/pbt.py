@@ -27,9 +27,27 @@ and the initial hyperparameter draw of train.py:320-351).
   every rank, initialised from train policy j mod P as train_state.py:489-498
   tiles them) hold a policy state without optimizer state; each call picks a
   uniform train policy and overwrites the least fit past slot with it when
-  _check_overwrite passes.  Past policies are snapshots only: past-play
-  matchmaking (pbt.py:135-247) is outside the fused path, so no env plays
-  them and their fitness stays what was copied.
+  _check_overwrite passes.  Under cross-play / past-play matchmaking the past
+  slots are opponents: each carries its own compute weight images and
+  descriptor (``PolicyImages``), refreshed in place by every snapshot, so the
+  prepared descriptor table and captured graphs stay valid.
+* ``PBTMatchmakeConfig`` / ``pbt_init_matchmaking`` / ``pbt_update_matchmaking``
+  (pbt.py:21-255, 346-379): the sim rows are laid out [self | cross | past]
+  (no static play), every region as matches of num_teams x team_size agents.
+  Team 0 of a cross-play or past-play match always plays the match's base
+  train policy (match m of a region of M matches: policy m // (M / P)) and is
+  the only team whose rows are stored for training; each team k >= 1 of a
+  cross-play match draws uniformly from the other P - 1 train policies (draw
+  in [0, P - 1), plus 1 where >= base), of a past-play match uniformly in
+  [P, P + Q).  On update there is one draw per (match, team k >= 1), applied
+  per agent where that agent's done is set; team 0 and the self-play region
+  never change.  ``mlearn_matchmake_update`` does the update on the device.
+* Fitness under teams: with num_teams == 2, episode results from the sim and
+  ``Policy.get_episode_scores``, ``TrainStateManager.elos`` (f32 [P + Q],
+  1500 at the start) follows ``pbt_update_elo`` every step; ``check_overwrite``
+  then takes its Elo form (pbt.py:566-571: expected win rate >=
+  policy_overwrite_threshold), the cull and the past update rank by rating
+  and a snapshot copies its source's rating to the slot.
 
 RNG: jax.random's threefry splits are replaced by Philox4x32-10 counters
 (the C ABI's ``mlearn_philox4x32_host``): the population key is
@@ -39,6 +57,15 @@ hyperparameter i) the words of counter {c, s, q, 0}: word 0 decides
 resample vs perturb, word 1 is the value's uniform; pbt_past_update's
 source pick uses slot 0, stream 0x7fffffff.  Uniforms are
 ``u32_to_unit`` (csrc/common.h).  oracle/pbt_ref.py restates all of it.
+
+Matchmaking draws from a stream of its own: the key is
+``train._split_seed(cfg.seed, MATCHMAKE_STREAM)`` (an index no other stream
+uses).  The draw of env step ``s`` (the rollout step counter, 64 bit) for
+match ``m`` of a region (index within the region) and team ``k`` >= 1 is word
+0 of Philox counter {s lo, s hi, m, region << 16 | k}, region 1 = cross play,
+2 = past play; the opponent is ``mulhi(word0, n)`` (the high 32 bits of the
+32 x 32 product) with n = P - 1 or Q: integer only, so host and device agree
+bit for bit.  Initialisation draws with s = 2^64 - 1.
 """
 
 import dataclasses
@@ -90,6 +117,218 @@ def _split(pbt_rng):
 def _draws(key, op, slot, stream):
     w = philox_host([[op & 0xFFFFFFFF, slot & 0xFFFFFFFF, stream & 0xFFFFFFFF, 0]], *key)[0]
     return u32_to_unit(w[0]), u32_to_unit(w[1])
+
+
+# ---------------------------------------------------------------------------
+# matchmaking
+# ---------------------------------------------------------------------------
+MATCHMAKE_STREAM = 0x4D4D  # train._split_seed index of the matchmaking key
+MATCHMAKE_INIT_STEP = (1 << 64) - 1
+REGION_CROSS, REGION_PAST = 1, 2
+ELO_INIT = 1500.0
+
+
+@dataclasses.dataclass(frozen=True)
+class PBTMatchmakeConfig:  # pbt.py:21-118
+    num_current_policies: int
+    num_past_policies: int
+    total_num_policies: int
+    num_teams: int
+    team_size: int
+
+    self_play_portion: float
+    cross_play_portion: float
+    past_play_portion: float
+    static_play_portion: float
+
+    self_play_batch_size: int
+    cross_play_batch_size: int
+    past_play_batch_size: int
+    static_play_batch_size: int
+
+    num_cross_play_matches: int
+    num_past_play_matches: int
+    num_static_play_matches: int
+    num_total_matches: int
+
+    complex_matchmaking: bool
+
+    custom_policy_ids: Any
+
+    @staticmethod
+    def setup(num_current_policies, num_past_policies, num_teams, team_size, sim_batch_size,
+              self_play_portion, cross_play_portion, past_play_portion, static_play_portion,
+              custom_policy_ids=()):
+        total_num_policies = num_current_policies + num_past_policies
+
+        assert (self_play_portion + cross_play_portion +
+                past_play_portion + static_play_portion == 1.0)
+
+        self_play_batch_size = int(sim_batch_size * self_play_portion)
+        cross_play_batch_size = int(sim_batch_size * cross_play_portion)
+        past_play_batch_size = int(sim_batch_size * past_play_portion)
+        static_play_batch_size = int(sim_batch_size * static_play_portion)
+
+        assert (self_play_batch_size + cross_play_batch_size + past_play_batch_size +
+                static_play_batch_size == sim_batch_size)
+
+        agents_per_world = num_teams * team_size
+
+        assert cross_play_batch_size % agents_per_world == 0
+        assert past_play_batch_size % agents_per_world == 0
+        assert static_play_batch_size % agents_per_world == 0
+
+        num_cross_play_matches = cross_play_batch_size // agents_per_world
+        num_past_play_matches = past_play_batch_size // agents_per_world
+        num_static_play_matches = static_play_batch_size // agents_per_world
+
+        num_total_matches = sim_batch_size // agents_per_world
+
+        assert num_cross_play_matches % num_current_policies == 0
+        assert num_past_play_matches % num_current_policies == 0
+
+        return PBTMatchmakeConfig(
+            num_current_policies=num_current_policies,
+            num_past_policies=num_past_policies,
+            total_num_policies=total_num_policies,
+            num_teams=num_teams,
+            team_size=team_size,
+            self_play_portion=self_play_portion,
+            cross_play_portion=cross_play_portion,
+            past_play_portion=past_play_portion,
+            static_play_portion=static_play_portion,
+            self_play_batch_size=self_play_batch_size,
+            cross_play_batch_size=cross_play_batch_size,
+            past_play_batch_size=past_play_batch_size,
+            static_play_batch_size=static_play_batch_size,
+            num_cross_play_matches=num_cross_play_matches,
+            num_past_play_matches=num_past_play_matches,
+            num_static_play_matches=num_static_play_matches,
+            num_total_matches=num_total_matches,
+            complex_matchmaking=self_play_portion != 1.0,
+            custom_policy_ids=tuple(custom_policy_ids or ()),
+        )
+
+
+def _mm_check(mm):
+    """The limits of the matchmaking here on top of setup's asserts."""
+    if mm.static_play_batch_size > 0:
+        raise NotImplementedError("matchmaking: static play is not part of training here")
+    if mm.cross_play_batch_size > 0 and mm.num_current_policies < 2:
+        raise ValueError("cross play needs at least two train policies")
+    if mm.past_play_batch_size > 0 and mm.num_past_policies < 1:
+        raise ValueError("past play needs at least one past policy")
+    if mm.num_teams < 2 and mm.cross_play_batch_size + mm.past_play_batch_size > 0:
+        raise ValueError("cross play / past play need at least two teams")
+    if mm.num_teams > 0xFFFF:
+        raise ValueError("matchmaking: at most 65535 teams")
+
+
+def _self_play_assignments(mm, batch_size):  # pbt.py:130-133
+    P = mm.num_current_policies
+    return np.repeat(np.arange(P, dtype=np.int32), batch_size // P)
+
+
+def matchmake_draws(key, step, region, num_matches, num_teams, n):
+    """mulhi(word 0, n) of Philox counter {step lo, step hi, match, region << 16
+    | team} for every (match, team >= 1): int32 [num_matches][num_teams - 1]."""
+    m, k = np.meshgrid(np.arange(num_matches, dtype=np.uint64),
+                       np.arange(1, num_teams, dtype=np.uint64), indexing="ij")
+    step = int(step) & 0xFFFFFFFFFFFFFFFF
+    ctr = np.empty((m.size, 4), dtype=np.uint32)
+    ctr[:, 0] = step & 0xFFFFFFFF
+    ctr[:, 1] = step >> 32
+    ctr[:, 2] = m.reshape(-1)
+    ctr[:, 3] = (int(region) << 16) | k.reshape(-1)
+    if m.size == 0:
+        return np.zeros((num_matches, num_teams - 1), dtype=np.int32)
+    w = philox_host(ctr, *key)[:, 0].astype(np.uint64)
+    return ((w * np.uint64(n)) >> np.uint64(32)).astype(np.int32).reshape(num_matches,
+                                                                          num_teams - 1)
+
+
+def _region_opponents(mm, key, step, region, base):
+    """New opponents [matches][teams - 1] of a region whose matches' team 0
+    plays ``base`` [matches]."""
+    P, Q = mm.num_current_policies, mm.num_past_policies
+    if region == REGION_CROSS:
+        d = matchmake_draws(key, step, region, base.shape[0], mm.num_teams, P - 1)
+        return np.where(d >= base[:, None], d + 1, d).astype(np.int32)
+    return (P + matchmake_draws(key, step, region, base.shape[0], mm.num_teams, Q)).astype(np.int32)
+
+
+def _regions(mm):
+    c0 = mm.self_play_batch_size
+    p0 = c0 + mm.cross_play_batch_size
+    return ((REGION_CROSS, c0, p0, mm.num_cross_play_matches),
+            (REGION_PAST, p0, p0 + mm.past_play_batch_size, mm.num_past_play_matches))
+
+
+def pbt_init_matchmaking(key, mm):
+    """pbt.py:125-208 (no static play): the initial int32 [N] assignments."""
+    _mm_check(mm)
+    out = [_self_play_assignments(mm, mm.self_play_batch_size)]
+    for region, start, stop, M in _regions(mm):
+        if stop == start:
+            continue
+        a = _self_play_assignments(mm, stop - start).reshape(M, mm.num_teams, mm.team_size)
+        a = a.copy()
+        a[:, 1:, :] = _region_opponents(mm, key, MATCHMAKE_INIT_STEP, region,
+                                        a[:, 0, 0])[:, :, None]
+        out.append(a.reshape(-1))
+    return np.concatenate(out).astype(np.int32)
+
+
+def pbt_update_matchmaking(assignments, dones, key, step, mm):
+    """pbt.py:210-255, 346-379: the assignments after env step ``step``; one
+    draw per (match, team >= 1), taken by the agents whose done is set."""
+    a = np.array(assignments, dtype=np.int32).reshape(-1)
+    d = np.asarray(dones).reshape(-1) != 0
+    for region, start, stop, M in _regions(mm):
+        if stop == start:
+            continue
+        ar = a[start:stop].reshape(M, mm.num_teams, mm.team_size)
+        dr = d[start:stop].reshape(M, mm.num_teams, mm.team_size)
+        new = _region_opponents(mm, key, step, region, ar[:, 0, 0])
+        ar[:, 1:, :] = np.where(dr[:, 1:, :], new[:, :, None], ar[:, 1:, :])
+    return a
+
+
+def num_train_agents_per_policy(mm):
+    """rollouts.py:1054-1068: the A store columns of every train policy (its
+    self-play rows and team 0 of its cross-play and past-play matches)."""
+    assert mm.cross_play_batch_size % mm.num_teams == 0
+    assert mm.past_play_batch_size % mm.num_teams == 0
+    total = (mm.self_play_batch_size + mm.cross_play_batch_size // mm.num_teams +
+             mm.past_play_batch_size // mm.num_teams)
+    assert total % mm.num_current_policies == 0
+    return total // mm.num_current_policies
+
+
+def sim_to_train_indices(mm):
+    """rollouts.py:1071-1104: int32 [P][A], the sim row of every store column."""
+    P = mm.num_current_policies
+    c0 = mm.self_play_batch_size
+    p0 = c0 + mm.cross_play_batch_size
+    p1 = p0 + mm.past_play_batch_size
+    idx = np.arange(p1, dtype=np.int32)
+
+    def matches(start, stop):
+        return idx[start:stop].reshape(P, -1, mm.num_teams, mm.team_size)
+
+    return np.concatenate([matches(0, c0).reshape(P, -1),
+                           matches(c0, p0)[:, :, 0, :].reshape(P, -1),
+                           matches(p0, p1)[:, :, 0, :].reshape(P, -1)], axis=1)
+
+
+def train_columns(mm):
+    """int32 [N]: the store column of every sim row (p * A + a for row
+    sim_to_train_indices[p][a]), -1 for opponent rows."""
+    s2t = sim_to_train_indices(mm).reshape(-1)
+    N = (mm.self_play_batch_size + mm.cross_play_batch_size + mm.past_play_batch_size)
+    col = np.full(N, -1, dtype=np.int32)
+    col[s2t] = np.arange(s2t.shape[0], dtype=np.int32)
+    return col
 
 
 # ---------------------------------------------------------------------------
@@ -261,10 +500,16 @@ def pbt_update_elo(get_episode_scores, assignments, dones, episode_results, elos
     return (e + diffs.sum(dim=1)).to(torch.float32)
 
 
-def check_overwrite(cfg, mean, var, N, src, dst):
-    """_check_overwrite (pbt.py:565-600), episode-score form: one-sided test
-    of the score difference, overwrite when p < 0.20 (float32)."""
+def check_overwrite(cfg, mean, var, N, src, dst, elos=None):
+    """_check_overwrite (pbt.py:565-600).  Episode-score form: one-sided test
+    of the score difference, overwrite when p < 0.20 (float32).  Elo form
+    (``elos`` given, pbt.py:566-571): src's expected win rate against dst >=
+    cfg.pbt.policy_overwrite_threshold (float32)."""
     f = np.float32
+    if elos is not None:
+        e = np.asarray(elos, np.float32)
+        exp = f(1.0) / (f(1.0) + np.power(f(10.0), (e[dst] - e[src]) / f(400.0), dtype=f))
+        return bool(f(exp) >= f(cfg.pbt.policy_overwrite_threshold))
     with np.errstate(divide="ignore", invalid="ignore"):
         s2 = f(var[src]) / f(N[src]) + f(var[dst]) / f(N[dst])
         t = (f(mean[src]) - f(mean[dst])) / np.sqrt(f(s2))
@@ -374,13 +619,20 @@ def gather_fitness(tsm, P):
     return mean, var, N
 
 
-def cull_plan(cfg, mean, var, N, P, num_cull):
+def cull_plan(cfg, mean, var, N, P, num_cull, elos=None):
     """[(dst, src, overwrite)]: the num_cull least fit train policies (stable
-    argsort of the fitness, pbt.py:618-622) against the most fit ones."""
-    order = np.argsort(np.asarray(mean, np.float32)[:P], kind="stable")
+    argsort of the fitness, pbt.py:618-622) against the most fit ones; the
+    fitness is the Elo rating when ``elos`` is given (pbt.py:602-606)."""
+    fit = mean if elos is None else elos
+    order = np.argsort(np.asarray(fit, np.float32)[:P], kind="stable")
     bottom, top = order[:num_cull], order[P - num_cull:]
-    return [(int(d), int(s), check_overwrite(cfg, mean, var, N, int(s), int(d)))
+    return [(int(d), int(s), check_overwrite(cfg, mean, var, N, int(s), int(d), elos=elos))
             for d, s in zip(bottom, top)]
+
+
+def _elos_host(tsm):
+    e = getattr(tsm, "elos", None)
+    return None if e is None else e.detach().cpu().numpy().astype(np.float32)
 
 
 def pbt_cull_update(cfg, tsm, num_cull_policies: int):
@@ -389,13 +641,16 @@ def pbt_cull_update(cfg, tsm, num_cull_policies: int):
     P = int(cfg.pbt.num_train_policies)
     assert 2 * num_cull_policies <= P
     mean, var, N = gather_fitness(tsm, P)
-    plan = cull_plan(cfg, mean, var, N, P, num_cull_policies)
+    elos = _elos_host(tsm)
+    plan = cull_plan(cfg, mean, var, N, P, num_cull_policies, elos=elos)
     k0, k1, op = _split(tsm.pbt_rng)
     # every copy reads the pre-cull state of its source (top and bottom are disjoint)
     for i, (dst, src, ok) in enumerate(plan):
         if not ok:
             continue
         copy_policy(tsm, src, dst, P)
+        if elos is not None:
+            tsm.elos[dst] = float(elos[src])
         for ps, ts in zip(tsm.policy_list, tsm.train_list):
             if ts.policy_id == dst:
                 pbt_explore_hyperparams(cfg, (k0, k1, op, i), ps, ts, CULL_RESAMPLE_CHANCE)
@@ -416,6 +671,23 @@ class PastPolicy:
         self.obs_est = None if like.obs_est is None else torch.zeros_like(like.obs_est)
         self.obs_count = None if like.obs_est is None else torch.zeros_like(like.obs_count)
         self.episode_score = MovingEpisodeScore(like.params.device)
+        # the slot as an opponent: its own weight images and descriptor, built
+        # once (the pointers never change) and refreshed by sync_weights
+        self.images = None
+        if getattr(like, "arch", None) is not None and not getattr(like, "recurrent", False) \
+                and not getattr(like, "generic", False):
+            from .train_state import PolicyImages
+            self.arch = like.arch
+            self.device = like.device
+            self.images = PolicyImages(like.arch, like.layout, self.params, self.obs_est)
+            self.desc = self.images.desc
+            self.sync_weights()
+
+    recurrent = False
+
+    def sync_weights(self):
+        if self.images is not None:
+            self.images.sync(self.params)
 
     def tensors(self):
         t = [self.params]
@@ -429,6 +701,7 @@ class PastPolicy:
     def load_state_dict(self, sd):
         for a, b in zip(self.tensors(), sd["tensors"]):
             a.copy_(b)
+        self.sync_weights()
 
 
 def _policy_tensors(ps):
@@ -454,6 +727,9 @@ def snapshot_policy(tsm, src_pid, past, P, fitness=None):
     if W > 1:
         for t in past.tensors():
             dist.broadcast(t, root)
+    past.sync_weights()
+    if getattr(tsm, "elos", None) is not None:
+        tsm.elos[past.policy_id] = tsm.elos[src_pid]
     if fitness is not None:
         mean, var, N = fitness
         e = past.episode_score
@@ -476,14 +752,16 @@ def init_past_policies(cfg, tsm):
     return tsm
 
 
-def past_update_plan(key, op, mean, var, N, P, Q):
-    """(src, dst, overwrite) of pbt_past_update; mean / var / N cover the P
-    train then the Q past policies."""
+def past_update_plan(key, op, mean, var, N, P, Q, cfg=None, elos=None):
+    """(src, dst, overwrite) of pbt_past_update; mean / var / N (and ``elos``,
+    the fitness when given) cover the P train then the Q past policies."""
     u, _ = _draws(key, op, 0, 0x7FFFFFFF)
     src = min(int(np.float32(u) * np.float32(P)), P - 1)  # random.randint(0, P)
-    dst = P + int(np.argmin(np.asarray(mean, np.float32)[P:P + Q]))  # jnp.argmin: first minimum
+    fit = mean if elos is None else elos
+    dst = P + int(np.argmin(np.asarray(fit, np.float32)[P:P + Q]))  # jnp.argmin: first minimum
     with np.errstate(divide="ignore", invalid="ignore"):
-        return src, dst, check_overwrite(cfg=None, mean=mean, var=var, N=N, src=src, dst=dst)
+        return src, dst, check_overwrite(cfg=cfg, mean=mean, var=var, N=N, src=src, dst=dst,
+                                         elos=elos)
 
 
 def pbt_past_update(cfg, tsm):
@@ -502,7 +780,8 @@ def pbt_past_update(cfg, tsm):
     mean = np.concatenate([mean, [float(x.mean[0]) for x in e]])
     var = np.concatenate([var, [float(x.var[0]) for x in e]])
     N = np.concatenate([N, [float(x.N[0]) for x in e]])
-    src, dst, ok = past_update_plan((k0, k1), op, mean, var, N, P, Q)
+    elos = _elos_host(tsm)
+    src, dst, ok = past_update_plan((k0, k1), op, mean, var, N, P, Q, cfg=cfg, elos=elos)
     if ok:
         snapshot_policy(tsm, src, tsm.past_list[dst - P], P, fitness=fit)
     tsm.last_past_update = (src, dst, ok)

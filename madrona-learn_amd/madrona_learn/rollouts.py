@@ -8,6 +8,16 @@ sim's step runs inside the same launch instead, envs.DummyVecEnv.native_step).  
 and the rollout metrics.  No finalize transpose (rollouts.py:786-804): the
 store stays [T][N] = [C][T/C][P][B] and the PPO kernels index sequences
 directly.
+
+Under cross-play / past-play matchmaking (``RolloutConfig.pbt.
+complex_matchmaking``, pbt.py) the sim steps N rows laid out [self | cross |
+past] while the store holds only the P * A train columns (each policy's
+self-play rows and team 0 of its matches, ``sim_to_train_indices``): per step
+one matched policy launch (mlearn_policy_rollout_step_matched) writes the
+store through that index and the sim-order actions, the user's sim steps, the
+Elo ratings follow the matches that ended and mlearn_matchmake_update redraws
+their opponents in ``RolloutState.policy_assignments``.  Everything after the
+rollout is the same code on the narrower store.
 """
 
 import math
@@ -18,7 +28,9 @@ import torch
 
 from . import _native as nat
 from .algo_common import compute_advantages, compute_returns
+from . import pbt as _pbt
 from .cfg import DiscreteActionsConfig
+from .pbt import PBTMatchmakeConfig
 
 
 @dataclass(frozen=True)
@@ -41,14 +53,20 @@ class RolloutConfig:  # rollouts.py:28-134 (self-play / single-policy path)
               static_play_portion, reward_gamma, custom_policy_ids, policy_dtype,
               reward_dtype=torch.float32, prob_dtype=torch.float32,
               policy_chunk_size_override=0):
-        complex_mm = (num_current_policies > 1 and self_play_portion != 1.0) or \
-            num_past_policies > 0 or cross_play_portion > 0 or past_play_portion > 0 or \
-            static_play_portion > 0
-        if complex_mm:
+        if static_play_portion > 0:
             raise NotImplementedError(
-                "cross-play / past-play matchmaking (pbt.py:135-247) is outside the fused "
-                "path; populations use the self-play split (pbt.py:130-133): policy p owns "
-                "env columns [p*B, (p+1)*B)")
+                "static play (pbt.py:204-205) is not part of training here; eval_policies "
+                "plays static assignments")
+        # self play only: the self-play split (pbt.py:130-133), policy p owns env
+        # columns [p*B, (p+1)*B); otherwise rows are [self | cross | past] and
+        # train policy p owns the store columns [p*A, (p+1)*A) of its self-play
+        # rows and team 0 of its matches (num_train_agents_per_policy)
+        mm = PBTMatchmakeConfig.setup(
+            num_current_policies=num_current_policies, num_past_policies=num_past_policies,
+            num_teams=num_teams, team_size=team_size, sim_batch_size=sim_batch_size,
+            self_play_portion=self_play_portion, cross_play_portion=cross_play_portion,
+            past_play_portion=past_play_portion, static_play_portion=static_play_portion,
+            custom_policy_ids=custom_policy_ids)
         assert sim_batch_size % num_current_policies == 0
         policy_chunk_size = sim_batch_size // num_current_policies  # rollouts.py:104-108
         if policy_chunk_size_override != 0:
@@ -65,12 +83,24 @@ class RolloutConfig:  # rollouts.py:28-134 (self-play / single-policy path)
             policy_dtype=policy_dtype,
             reward_dtype=reward_dtype,
             prob_dtype=prob_dtype,
+            pbt=mm,
         )
+
+
+def num_train_agents_per_policy(cfg):  # rollouts.py:1054-1068
+    """A: the store columns of every train policy (cfg: RolloutConfig)."""
+    return _pbt.num_train_agents_per_policy(cfg.pbt)
+
+
+def sim_to_train_indices(cfg):  # rollouts.py:1071-1104
+    """int32 [P][A]: the sim row of every store column (cfg: RolloutConfig)."""
+    return _pbt.sim_to_train_indices(cfg.pbt)
 
 
 class RolloutState:  # rollouts.py:171-309
     def __init__(self, cfg, step_fn, sim_state, cur_obs, prng_key, rnn_states, sim_ctrl,
-                 env_returns, counters, policy_assignments, native_step=None):
+                 env_returns, counters, policy_assignments, native_step=None,
+                 matchmake_key=None):
         self.cfg = cfg
         self.step_fn = step_fn
         # the built-in synthetic sim's fused step (envs.DummyVecEnv.native_step),
@@ -83,13 +113,26 @@ class RolloutState:  # rollouts.py:171-309
         self.sim_ctrl = sim_ctrl
         self.env_returns = env_returns
         self.counters = counters  # device int64[8]: [0] rollout step, [1] epoch
+        # int32 [N, 1]; under cross-play / past-play matchmaking the live
+        # assignments, redrawn in place where matches end (matchmake_key: the
+        # Philox key of those draws)
         self.policy_assignments = policy_assignments
+        self.matchmake_key = matchmake_key
 
     @staticmethod
     def create(rollout_cfg, sim_fns, prng_key, rnn_states, init_sim_ctrl,
-               static_play_assignments=None, device="cuda"):
+               static_play_assignments=None, device="cuda", matchmake_key=None):
         init_out = sim_fns["init"]()
         dev = torch.device(device)
+        mm = rollout_cfg.pbt
+        if mm is not None and mm.complex_matchmaking:
+            if matchmake_key is None:
+                raise ValueError("cross-play / past-play matchmaking needs a matchmake_key")
+            assign = torch.from_numpy(_pbt.pbt_init_matchmaking(matchmake_key, mm)).to(
+                dev).reshape(rollout_cfg.sim_batch_size, 1)
+        else:
+            # self-play: every agent runs policy 0 (pbt.py:130-133)
+            assign = torch.zeros((rollout_cfg.sim_batch_size, 1), dtype=torch.int32, device=dev)
         return RolloutState(
             cfg=rollout_cfg,
             step_fn=sim_fns["step"],
@@ -100,10 +143,9 @@ class RolloutState:  # rollouts.py:171-309
             sim_ctrl=init_sim_ctrl,
             env_returns=torch.zeros(rollout_cfg.sim_batch_size, dtype=torch.float32, device=dev),
             counters=torch.zeros(8, dtype=torch.int64, device=dev),
-            # self-play: every agent runs policy 0 (pbt.py:130-133)
-            policy_assignments=torch.zeros((rollout_cfg.sim_batch_size, 1), dtype=torch.int32,
-                                           device=dev),
+            policy_assignments=assign,
             native_step=sim_fns.get("native_step"),
+            matchmake_key=matchmake_key,
         )
 
 
@@ -262,7 +304,8 @@ class RolloutManager:  # rollouts.py:373-826
     rollout_kernel = 0
     population_launch = True
 
-    def __init__(self, train_cfg, init_rollout_state: RolloutState, policy_states, env_offset=0):
+    def __init__(self, train_cfg, init_rollout_state: RolloutState, policy_states, env_offset=0,
+                 past_policies=None):
         self.train_cfg = train_cfg
         self._cfg = init_rollout_state.cfg
         assert train_cfg.steps_per_update % train_cfg.num_bptt_chunks == 0  # rollouts.py:387
@@ -276,6 +319,19 @@ class RolloutManager:  # rollouts.py:373-826
         if self.N % self.P != 0:
             raise ValueError(f"{self.N} envs do not split over {self.P} policies")
         self.B = self.N // self.P
+        # cross-play / past-play matchmaking (pbt.PBTMatchmakeConfig): the sim
+        # steps N rows, the store holds the NT = P * A train columns (policy
+        # p's self-play rows and team 0 of its matches, sim_to_train_indices);
+        # everything downstream of the rollout runs on that store unchanged
+        mm = self._cfg.pbt
+        self.matched = bool(mm is not None and mm.complex_matchmaking)
+        self.NT = self.N
+        if self.matched:
+            if self.P != mm.num_current_policies:
+                raise ValueError(f"matchmaking over {mm.num_current_policies} train policies, "
+                                 f"got {self.P} policy states")
+            self.B = _pbt.num_train_agents_per_policy(mm)
+            self.NT = self.P * self.B
         self.policy_state = self.policies[0]
         self.prefix = getattr(self.policy_state.actor_critic.backbone, "prefix", None)
         for ps in self.policies:
@@ -283,7 +339,7 @@ class RolloutManager:  # rollouts.py:373-826
         arch = self.policy_state.arch
         for ps in self.policies[1:]:
             assert ps.arch == arch, "population policies must share one architecture"
-        self.store = RolloutStore(self.T, self.N, arch.obs_dim, arch.num_groups, arch.dtype,
+        self.store = RolloutStore(self.T, self.NT, arch.obs_dim, arch.num_groups, arch.dtype,
                                   self.policy_state.device, self.C, arch.lstm_hidden)
         # GAE without a value normaliser: returns not materialised (RolloutStore)
         self.store.derive_returns = bool(train_cfg.compute_advantages and
@@ -325,9 +381,95 @@ class RolloutManager:  # rollouts.py:373-826
                     jobs[i].x2 = s.advantages.data_ptr() + c0 * 4
                 jobs[i].n = n
                 jobs[i].cols = cols if self.P > 1 else 0
-                jobs[i].ld = self.N
+                jobs[i].ld = self.NT
                 jobs[i].abs_value = 0
             self._jobs.append(jobs)
+        if self.matched:
+            self._init_matched(init_rollout_state, list(past_policies or []))
+
+    def _init_matched(self, rollout_state, past):
+        from .train_state import MatchedRolloutStep
+        mm = self._cfg.pbt
+        ps0 = self.policy_state
+        if getattr(ps0, "generic", False) or self.R:
+            raise NotImplementedError("matchmaking: feed-forward policies on the fused kernels")
+        if any(ps.obs_est is not None for ps in self.policies):
+            raise NotImplementedError("matchmaking: no ObservationsEMANormalizer (the gathered "
+                                      "step has no statistics pass)")
+        if len(past) != mm.num_past_policies:
+            raise ValueError(f"matchmaking over {mm.num_past_policies} past policies, got "
+                             f"{len(past)}")
+        dev = ps0.device
+        self.train_col = torch.from_numpy(_pbt.train_columns(mm)).to(dev)
+        self._matched = MatchedRolloutStep(self.policies + past, self.N, self.train_col)
+        self._sim_act = torch.zeros((self.N, ps0.arch.num_groups), dtype=torch.int32, device=dev)
+        c = nat.MatchmakeCfg()
+        c.self_play_batch_size = mm.self_play_batch_size
+        c.cross_play_batch_size = mm.cross_play_batch_size
+        c.past_play_batch_size = mm.past_play_batch_size
+        c.num_current_policies = mm.num_current_policies
+        c.num_past_policies = mm.num_past_policies
+        c.num_teams, c.team_size = mm.num_teams, mm.team_size
+        self._mm_desc = c
+        a = rollout_state.policy_assignments
+        if a.dtype != torch.int32 or a.numel() != self.N or not a.is_contiguous():
+            raise ValueError("matchmaking: RolloutState.policy_assignments must be int32 [N, 1]")
+
+    def _collect_matched(self, tsm, rollout_state, gamma):
+        """One rollout under matchmaking: per env step the matched policy step
+        (with the post-step of the step before), the sim, the Elo update and
+        the matchmaking update; then the bootstrap critic."""
+        s = self.store
+        L = nat.lib()
+        mm = self._cfg.pbt
+        key = rollout_state.prng_key
+        mk = rollout_state.matchmake_key
+        step_ctr = rollout_state.counters[0:1]
+        asg = rollout_state.policy_assignments
+        if not hasattr(self, "_mposts"):
+            self._mposts = [nat.PostStep() for _ in range(self.T)]
+            self._post_keep = [None] * self.T
+        post = None
+        for t in range(self.T):
+            obs = self.prep_obs(rollout_state.cur_obs)
+            self._matched.step(asg, obs, s.obs[t], s.actions[t], s.log_probs[t], s.values[t],
+                               self._sim_act, key, step_ctr, t, self.env_offset, sample=True,
+                               post=post)
+            out = rollout_state.step_fn({
+                "state": rollout_state.sim_state,
+                "actions": self._sim_actions(t, self._sim_act),
+                "resets": self._resets,
+                "sim_ctrl": rollout_state.sim_ctrl,
+                "pbt": {"policy_assignments": asg},
+            })
+            rew = out["rewards"].reshape(-1)
+            if rew.dtype != torch.float32:
+                rew = rew.float()
+            dn = out["dones"].reshape(-1)
+            dn = dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)
+            rew, dn = rew.contiguous(), dn.contiguous()
+            post = self._mposts[t]
+            post.rewards, post.dones = nat.ptr(rew), nat.ptr(dn)
+            post.store_rewards, post.store_dones = nat.ptr(s.rewards[t]), nat.ptr(s.dones[t])
+            post.env_returns = nat.ptr(rollout_state.env_returns)
+            post.env_returns_trace = nat.ptr(s.env_returns_trace[t])
+            post.gamma = gamma
+            self._post_keep[t] = (rew, dn)
+            rollout_state.sim_state = out["state"]
+            rollout_state.cur_obs = out["obs"]
+            # ratings from the matches that ended, under the assignments they
+            # were played with (pbt.py:273-343), then the opponents of the next ones
+            res = (out.get("pbt") or {}).get("episode_results")
+            elos = getattr(tsm, "elos", None)
+            if res is not None and elos is not None and \
+                    getattr(self, "get_episode_scores", None) is not None:
+                elos.copy_(_pbt.pbt_update_elo(self.get_episode_scores, asg, dn, res, elos,
+                                               mm.num_teams, mm.team_size))
+            nat.check(L.mlearn_matchmake_update(nat.ptr(asg), nat.ptr(dn), self._mm_desc, mk[0],
+                                                mk[1], nat.ptr(step_ctr), t, nat.stream_handle()),
+                      "matchmake_update")
+        obs = self.prep_obs(rollout_state.cur_obs)
+        self._matched.critic_only(asg, obs, s.bootstrap, post=post)
 
     def view(self, p=0):
         """Rollout view of policy p's env columns.  With compute_advantages=False
@@ -366,14 +508,15 @@ class RolloutManager:  # rollouts.py:373-826
             self._carries[key] = d
         return d
 
-    def _sim_actions(self, t):
-        """The sim's 'actions' input of step t: the [N, K] store slice, or with
-        several action groups a dict keyed like TrainConfig.actions of [N, K_g]
-        views (rollouts.py:985-1002)."""
+    def _sim_actions(self, t, a=None):
+        """The sim's 'actions' input of step t: the [N, K] store slice (or
+        ``a``, the sim-order actions under matchmaking), or with several
+        action groups a dict keyed like TrainConfig.actions of [N, K_g] views
+        (rollouts.py:985-1002)."""
         from .models import action_groups
         if not hasattr(self, "_act_groups"):
             self._act_groups = action_groups(self.train_cfg.actions)
-        a = self.store.actions[t]
+        a = self.store.actions[t] if a is None else a
         if len(self._act_groups) == 1:
             return a
         out, off = {}, 0
@@ -434,6 +577,9 @@ class RolloutManager:  # rollouts.py:373-826
             # a tree outside the fused kernels: torch modules per step (generic.py)
             from .generic import TorchRollout
             TorchRollout(self).collect(rollout_state, gamma)
+            return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
+        if self.matched:
+            self._collect_matched(train_state_mgr, rollout_state, gamma)
             return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
         key = rollout_state.prng_key
         step_ctr = rollout_state.counters[0:1]

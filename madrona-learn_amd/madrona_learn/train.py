@@ -280,6 +280,9 @@ class TrainingManager:  # train.py:35-64
         r = self.rollout
         out = {"counters": r.counters.cpu(), "env_returns": r.env_returns.cpu(),
                "cur_obs": _to_cpu(r.cur_obs), "rnn_states": _to_cpu(r.rnn_states)}
+        if r.matchmake_key is not None:
+            # the live matchmaking assignments (their step counter is counters[0])
+            out["policy_assignments"] = r.policy_assignments.cpu()
         get = getattr(self, "_sim_get_ckpts", None)
         if get is not None:
             out["sim"] = _to_cpu(get())
@@ -291,6 +294,8 @@ class TrainingManager:  # train.py:35-64
         r.env_returns.copy_(sd["env_returns"])
         _copy_into(r.cur_obs, sd["cur_obs"])
         _copy_into(r.rnn_states, sd["rnn_states"])
+        if r.matchmake_key is not None and sd.get("policy_assignments") is not None:
+            r.policy_assignments.copy_(sd["policy_assignments"])
         load = getattr(self, "_sim_load_ckpts", None)
         if load is not None and sd.get("sim") is not None:
             load(sd["sim"])
@@ -352,14 +357,12 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
             "hlgauss_critic (HLGaussDist, models.py:177-315) is outside the fused path; the "
             "scalar DenseLayerCritic and the DreamerV3Critic two-hot critic are supported")
     num_policies = 1
+    # cross-play / past-play matchmaking (pbt.py:21-255): any portion off pure self play
+    matched = False
     if cfg.pbt is not None:
         pbt = cfg.pbt
-        if pbt.self_play_portion != 1.0 or pbt.past_play_portion != 0.0 or \
-                pbt.cross_play_portion != 0.0:
-            raise NotImplementedError(
-                "populations run the self-play split (pbt.py:130-133); past/cross-play "
-                "matchmaking (pbt.py:135-247) is outside the fused path (past policies are "
-                "kept as snapshots, pbt_past_update)")
+        matched = pbt.self_play_portion != 1.0 or pbt.past_play_portion != 0.0 or \
+            pbt.cross_play_portion != 0.0
         num_policies = int(pbt.num_train_policies)
     # policy placement: which train policies this rank holds, and the ranks it
     # shares gradients with (dist.policy_placement)
@@ -375,18 +378,38 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
     if cfg.num_worlds % W != 0:
         raise ValueError(f"num_worlds={cfg.num_worlds} does not split over {W} ranks")
     sim_batch = cfg.num_agents_per_world * (cfg.num_worlds // W)
-    rollout_cfg = RolloutConfig.setup(
-        num_current_policies=len(policy_ids), num_past_policies=0, num_teams=1,
-        team_size=cfg.num_agents_per_world, sim_batch_size=sim_batch, actions_cfg=cfg.actions,
-        self_play_portion=1.0, cross_play_portion=0.0, past_play_portion=0.0,
-        static_play_portion=0.0, reward_gamma=cfg.gamma,
-        custom_policy_ids=cfg.custom_policy_ids, policy_dtype=cfg.compute_dtype)
-    rollout_key = _split_seed(cfg.seed, 1)
     rnn_states = policy.actor_critic.init_recurrent_state(sim_batch)
+    matchmake_key = None
+    if matched:
+        why = _matchmaking_problem(cfg, policy, rnn_states, W)
+        if why is not None:
+            raise NotImplementedError(f"cross-play / past-play matchmaking: {why}")
+        from .pbt import MATCHMAKE_STREAM
+        matchmake_key = _split_seed(cfg.seed, MATCHMAKE_STREAM)
+        rollout_cfg = RolloutConfig.setup(
+            num_current_policies=len(policy_ids), num_past_policies=int(pbt.num_past_policies),
+            num_teams=int(pbt.num_teams), team_size=int(pbt.team_size),
+            sim_batch_size=sim_batch, actions_cfg=cfg.actions,
+            self_play_portion=pbt.self_play_portion, cross_play_portion=pbt.cross_play_portion,
+            past_play_portion=pbt.past_play_portion, static_play_portion=0.0,
+            reward_gamma=cfg.gamma, custom_policy_ids=(), policy_dtype=cfg.compute_dtype)
+    else:
+        rollout_cfg = RolloutConfig.setup(
+            num_current_policies=len(policy_ids), num_past_policies=0, num_teams=1,
+            team_size=cfg.num_agents_per_world, sim_batch_size=sim_batch,
+            actions_cfg=cfg.actions, self_play_portion=1.0, cross_play_portion=0.0,
+            past_play_portion=0.0, static_play_portion=0.0, reward_gamma=cfg.gamma,
+            custom_policy_ids=cfg.custom_policy_ids, policy_dtype=cfg.compute_dtype)
+    rollout_key = _split_seed(cfg.seed, 1)
     rollout_state = RolloutState.create(rollout_cfg, sim_fns, rollout_key, rnn_states,
-                                        init_sim_ctrl, device=device)
+                                        init_sim_ctrl, device=device,
+                                        matchmake_key=matchmake_key)
 
     generic_why = _fused_tree_problem(policy, rollout_state, sim_batch, cfg)
+    if generic_why is not None and matched:
+        raise NotImplementedError(
+            "cross-play / past-play matchmaking: the torch path does not run it (the policy "
+            f"tree is outside the fused kernels: {generic_why})")
     if generic_why is not None:
         # a tree (or preprocess) the fused kernels do not implement: torch
         # autograd over the user's modules, HIP kernels around them (generic.py)
@@ -454,6 +477,11 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
         if cfg.pbt.num_past_policies > 0:
             from .pbt import init_past_policies
             init_past_policies(cfg, tsm)
+        if matched and int(pbt.num_teams) == 2 and policy.get_episode_scores is not None:
+            # Elo ratings of the train policies and the past slots (pbt.py:258-343)
+            from .pbt import ELO_INIT
+            tsm.elos = torch.full((num_policies + int(pbt.num_past_policies),), ELO_INIT,
+                                  dtype=torch.float32, device=device)
     start = 0
     ckpt_rollout = None
     if restore_ckpt is not None:
@@ -466,7 +494,8 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
         if ckpt_rollout is not None:
             rollout_state.counters[1].copy_(ckpt_rollout["counters"][1])
 
-    rollout_mgr = RolloutManager(cfg, rollout_state, pss, env_offset=rank * sim_batch)
+    rollout_mgr = RolloutManager(cfg, rollout_state, pss, env_offset=rank * sim_batch,
+                                 past_policies=tsm.past_list if matched else None)
     rollout_mgr.get_episode_scores = policy.get_episode_scores
     names = algos[0].add_metrics(cfg, [])
     names = rollout_mgr.add_metrics(cfg, names)
@@ -481,6 +510,24 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
     mgr._sim_get_ckpts = sim_fns.get("get_ckpts")
     mgr._sim_load_ckpts = sim_fns.get("load_ckpts")
     return mgr
+
+
+def _matchmaking_problem(cfg, policy, rnn_states, W):
+    """Why this configuration cannot train under cross-play / past-play
+    matchmaking, or None."""
+    from .observations import ObservationsEMANormalizer
+    pbt = cfg.pbt
+    if W > 1:
+        return f"single rank only (this job has {W} ranks)"
+    if any(True for _ in _leaves(rnn_states)):
+        return "recurrent policies are not supported (no carry per assignment)"
+    if isinstance(policy.obs_preprocess, ObservationsEMANormalizer):
+        return ("an ObservationsEMANormalizer is not supported (the gathered step has no "
+                "statistics pass)")
+    if int(pbt.num_teams) * int(pbt.team_size) != int(cfg.num_agents_per_world):
+        return (f"num_teams * team_size = {pbt.num_teams * pbt.team_size} must equal "
+                f"num_agents_per_world = {cfg.num_agents_per_world}")
+    return None
 
 
 def _fused_tree_problem(policy, rollout_state, sim_batch, cfg):

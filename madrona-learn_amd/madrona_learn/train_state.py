@@ -141,6 +141,50 @@ def compile_arch(actor_critic: ActorCritic, obs_dim: int, compute_dtype) -> MlpA
     return arch
 
 
+class PolicyImages:
+    """The compute-dtype weight images of a feed-forward parameter arena and
+    the ``mlearn_mlp_policy`` descriptor that binds them (LayerNorm parameters
+    and the normaliser estimates are read from ``params`` / ``obs_est``
+    directly).  Built once: ``sync`` rewrites the images in place, the
+    descriptor's pointers never change."""
+
+    def __init__(self, arch, layout, params, obs_est=None):
+        H, D, L = arch.hidden, arch.obs_dim, arch.num_layers
+        dt, dev = arch.dtype, params.device
+        self.w_t, self.w = [], []
+        for l in range(L):
+            fin = D if l == 0 else H
+            self.w_t.append(torch.zeros(H * fin, dtype=dt, device=dev))
+            self.w.append(torch.zeros(fin * H if l > 0 else 0, dtype=dt, device=dev))
+        HC = arch.head_cols
+        self.head_t = torch.zeros(HC * H, dtype=dt, device=dev)
+        self.head = torch.zeros(H * HC, dtype=dt, device=dev)
+        self.head_b = torch.zeros((HC,), dtype=torch.float32, device=dev)
+        d = nat.MlpPolicy()
+        d.dtype = nat.dtype_code(dt)
+        d.obs_dim = D
+        d.hidden = H
+        d.num_layers = L
+        d.critic_bins = arch.critic_bins
+        d.actions = nat.action_layout(arch.buckets)
+        for l in range(L):
+            d.w_t[l] = self.w_t[l].data_ptr()
+            d.w[l] = self.w[l].data_ptr() if l > 0 else None
+            d.ln_scale[l] = params.data_ptr() + 4 * layout["s"][l][0]
+            d.ln_bias[l] = params.data_ptr() + 4 * layout["b"][l][0]
+        d.head_t = self.head_t.data_ptr()
+        d.head = self.head.data_ptr()
+        d.head_bias = self.head_b.data_ptr()
+        if obs_est is not None:
+            d.obs_mu = obs_est.data_ptr()
+            d.obs_inv_sigma = obs_est.data_ptr() + 4 * D
+        self.desc = d
+
+    def sync(self, params):
+        nat.check(nat.lib().mlearn_policy_sync_weights(self.desc, nat.ptr(params),
+                                                       nat.stream_handle()), "sync_weights")
+
+
 class PolicyState:
     """Parameters + compute images of one policy (train_state.py:34-82)."""
 
@@ -182,32 +226,6 @@ class PolicyState:
 
         self.params = torch.from_numpy(host).to(self.device)
         self.init_norms = torch.tensor(init_norms, dtype=torch.float32, device=self.device)
-        # compute-dtype fragment-order images read by the kernels (frag.py)
-        self.w_t, self.w = [], []
-        for l in range(L):
-            fin = D if l == 0 else H
-            self.w_t.append(torch.zeros(H * fin, dtype=dt, device=self.device))
-            self.w.append(torch.zeros(fin * H if l > 0 else 0, dtype=dt, device=self.device))
-        HC = arch.head_cols
-        self.head_t = torch.zeros(HC * H, dtype=dt, device=self.device)
-        self.head = torch.zeros(H * HC, dtype=dt, device=self.device)
-        self.head_b = torch.zeros((HC,), dtype=torch.float32, device=self.device)
-
-        d = nat.MlpPolicy()
-        d.dtype = nat.dtype_code(dt)
-        d.obs_dim = D
-        d.hidden = H
-        d.num_layers = L
-        d.critic_bins = arch.critic_bins
-        d.actions = nat.action_layout(arch.buckets)
-        for l in range(L):
-            d.w_t[l] = self.w_t[l].data_ptr()
-            d.w[l] = self.w[l].data_ptr() if l > 0 else None
-            d.ln_scale[l] = self.params.data_ptr() + 4 * self.layout["s"][l][0]
-            d.ln_bias[l] = self.params.data_ptr() + 4 * self.layout["b"][l][0]
-        d.head_t = self.head_t.data_ptr()
-        d.head = self.head.data_ptr()
-        d.head_bias = self.head_b.data_ptr()
         # ObservationsEMANormalizer estimates (init_estimates, moving_avg.py:56-76):
         # [5][D] = mu, inv_sigma, sigma, mu_biased, sigma_sq_biased, + update count
         self.obs_est = self.obs_count = None
@@ -216,9 +234,13 @@ class PolicyState:
             self.obs_est = torch.zeros((5, D), dtype=torch.float32, device=self.device)
             self.obs_est[1:3] = 1.0
             self.obs_count = torch.zeros(1, dtype=torch.int32, device=self.device)
-            d.obs_mu = self.obs_est.data_ptr()
-            d.obs_inv_sigma = self.obs_est.data_ptr() + 4 * D
-        self.desc = d
+        # compute-dtype fragment-order images read by the kernels (frag.py)
+        self.images = PolicyImages(arch, self.layout, self.params, self.obs_est)
+        self.w_t, self.w = self.images.w_t, self.images.w
+        self.head_t, self.head, self.head_b = (self.images.head_t, self.images.head,
+                                               self.images.head_b)
+        HC = arch.head_cols
+        d = self.desc = self.images.desc
         # population fitness (MovingEpisodeScore, train_state.py:359-366)
         from .pbt import MovingEpisodeScore
         self.episode_score = MovingEpisodeScore(self.device)
@@ -461,6 +483,56 @@ class AssignedPolicyStep:
             "policy_step_assigned")
 
 
+class MatchedRolloutStep(AssignedPolicyStep):
+    """The assigned step as a full rollout step of league training
+    (mlearn_policy_rollout_step_matched): ``policy_states`` = the train
+    policies then the past slots (pbt.PastPolicy); ``train_col`` int32 [N] =
+    the store column of every sim row, -1 for opponent rows."""
+
+    def __init__(self, policy_states, N, train_col):
+        super().__init__(policy_states, N)
+        if train_col.dtype != torch.int32 or train_col.numel() != self.N:
+            raise ValueError("MatchedRolloutStep: train_col must be int32 [N]")
+        self.train_col = train_col.reshape(-1).contiguous()
+        self.num_cols = int((self.train_col >= 0).sum().item())
+        if int(self.train_col.max().item()) >= self.num_cols:
+            raise ValueError("MatchedRolloutStep: train_col must number the train columns "
+                             "0 .. count - 1")
+
+    def _call(self, assignments, obs, obs_store, sact, slogp, svals, actions, key, step_ctr, step,
+              env_offset, sample, post):
+        N = obs.shape[0]
+        if N != self.N:
+            raise ValueError(f"MatchedRolloutStep built for {self.N} rows, got {N}")
+        for t in (sact, slogp, svals):
+            if t is not None and t.shape[0] != self.num_cols:
+                raise ValueError(f"MatchedRolloutStep: a store row of {t.shape[0]} columns, "
+                                 f"expected {self.num_cols}")
+        nat.check(nat.lib().mlearn_policy_rollout_step_matched(
+            self.descs, self.P, nat.ptr(assignments, torch.int32, N, "assignments"),
+            nat.ptr(self.train_col), self.num_cols, nat.ptr(obs, torch.float32, name="obs"), N,
+            nat.ptr(obs_store), nat.ptr(sact, torch.int32), nat.ptr(slogp), nat.ptr(svals),
+            nat.ptr(actions, torch.int32), key[0], key[1], nat.ptr(step_ctr), step, env_offset,
+            1 if sample else 0, post, nat.ptr(self.workspace), nat.stream_handle()),
+            "policy_rollout_step_matched")
+
+    def step(self, assignments, obs, obs_store, store_actions, store_log_probs, store_values,
+             actions, key, step_ctr, step, env_offset=0, sample=True, post=None):
+        """One rollout step: store rows in train space ([num_cols, ...]),
+        ``actions`` [N, K] in sim order; ``post``: nat.PostStep of the previous
+        env step (rewards / dones / env_returns in sim order, the store rows and
+        the trace in train space)."""
+        if obs_store is not None and obs_store.shape[0] != self.num_cols:
+            raise ValueError("MatchedRolloutStep: obs_store rows != train columns")
+        self._call(assignments, obs, obs_store, store_actions, store_log_probs, store_values,
+                   actions, key, step_ctr, step, env_offset, sample, post)
+
+    def critic_only(self, assignments, obs, bootstrap, post=None):
+        """The bootstrap values of the train columns (no action is written)."""
+        self._call(assignments, obs, None, None, None, bootstrap, None, (0, 0), None, 0, 0,
+                   False, post)
+
+
 class PolicyTrainState:
     """Optimizer + per-policy training state (train_state.py:85-136)."""
 
@@ -554,6 +626,7 @@ class TrainStateManager:  # train_state.py:139-304
     user_state: Any = None
     value_norm: Any = None  # [P][8] f32 value-normaliser estimates (normalize_values)
     past_list: Any = None   # past-policy snapshots (pbt.PastPolicy), every rank
+    elos: Any = None        # f32 [P + Q] Elo ratings (two-team matchmaking), device
 
     @property
     def policy_list(self):
@@ -575,7 +648,8 @@ class TrainStateManager:  # train_state.py:139-304
                 "pbt_rng": self.pbt_rng if isinstance(self.pbt_rng, (torch.Tensor, type(None)))
                 else None,
                 "user_state": _ckpt_safe(self.user_state),
-                "past": [p.state_dict() for p in (self.past_list or [])]}
+                "past": [p.state_dict() for p in (self.past_list or [])],
+                "elos": None if self.elos is None else self.elos.detach().cpu()}
 
     def load_state_dict(self, sd):
         pol, tr = sd["policies"], sd["train"]
@@ -596,6 +670,8 @@ class TrainStateManager:  # train_state.py:139-304
                              f"{len(self.past_list or [])}")
         for p, d in zip(self.past_list or [], past):
             p.load_state_dict(d)
+        if self.elos is not None and sd.get("elos") is not None:
+            self.elos.copy_(sd["elos"])
         return self
 
     def save(self, update_idx, path, extra=None):  # train_state.py:145-163
