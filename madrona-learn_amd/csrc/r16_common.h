@@ -36,27 +36,16 @@ constexpr int kR16Ring0 = ML_R16_RING0;  // first-layer (L2) A fragments in flig
 #define ML_R16_RINGH 8
 #endif
 constexpr int kR16RingH = ML_R16_RINGH;  // head (L2, HC = 96) A fragments in flight
-// LDS: W1 image [256 rows = out][512 B], head image [32 rows = col][512 B],
-// LayerNorm scale/bias [2][2][256] f32, head bias [32] f32, per-wave logits
-// scratch [8][16][kR16LGS] bf16, the action groups' logit offsets, entropy
-// coefficients and objective weights (read per lane by the loss tasks: from
-// the kernel arguments a lane-dependent index would copy the arrays into
-// registers)
-constexpr size_t kR16OffW1 = 0;
-constexpr size_t kR16OffWh = kR16OffW1 + (size_t)kR16H * 512;
-constexpr size_t kR16OffGb = kR16OffWh + (size_t)kR16HC * 512;
-constexpr size_t kR16OffHb = kR16OffGb + (size_t)2 * 2 * kR16H * 4;
-constexpr size_t kR16OffLg = kR16OffHb + (size_t)kR16HC * 4;
-constexpr size_t kR16OffTab = kR16OffLg + (size_t)kR16Waves * 16 * kR16LGS * 2;
 constexpr int kR16TabN = 3 * (MLEARN_MAX_GROUPS + 1);  // group offsets, entropy coefs, obj weights
-constexpr size_t kR16Lds = kR16OffTab + (size_t)kR16TabN * 4;
-static_assert(kR16Lds <= 160 * 1024, "row-split step LDS budget");
-
-// The same layout for head width HC (the kR16Off* constants above are HC =
-// 32).  At HC = 96 (a DreamerV3 two-hot critic: A logits + up to 63 bins,
-// round 6) the 48 KB head image no longer fits beside W1 and a 16-row
-// logits scratch of 96 columns, so the head products stream the head image
-// from L2 (r16_head_l2) and LDS holds the critic's bin values instead.
+// LDS for head width HC: W1 image [256 rows = out][512 B], head image [32 rows
+// = col][512 B], LayerNorm scale/bias [2][2][256] f32, head bias [HC] f32,
+// per-wave logits scratch [8][16][LGS] bf16, the action groups' logit
+// offsets, entropy coefficients and objective weights (read per lane by the
+// loss tasks: from the kernel arguments a lane-dependent index would copy the
+// arrays into registers).  At HC = 96 (a DreamerV3 two-hot critic: A logits +
+// up to 63 bins, round 6) the 48 KB head image no longer fits beside W1 and a
+// 16-row logits scratch of 96 columns, so the head products stream the head
+// image from L2 (r16_head_l2) and LDS holds the critic's bin values instead.
 template <int HC> struct R16Lay {
     static_assert(HC == 32 || HC == 96, "head width");
     static constexpr int LGS = HC == 32 ? kR16LGS : 104;  // logits scratch row stride (bf16)
@@ -70,7 +59,6 @@ template <int HC> struct R16Lay {
     static constexpr size_t Lds = OffTab + (size_t)kR16TabN * 4;
     static_assert(Lds <= 160 * 1024, "row-split LDS budget");
 };
-static_assert(R16Lay<32>::Lds == kR16Lds && R16Lay<32>::OffLg == kR16OffLg, "layouts agree");
 
 typedef float f2v __attribute__((ext_vector_type(2)));
 typedef short short4r __attribute__((ext_vector_type(4)));

@@ -5,7 +5,7 @@
 // models.py:46-56, 99-154), Gumbel-max sampling (dists.py:26-52), the store
 // writes (_post_inference_cb 637-680), the sim step and _post_step_cb
 // (682-714, bookkeeping 933-973); then the bootstrap critic (607-635).
-// Included by policy.hip inside namespace ml after RollK.
+// Included by policy_rollout.h inside namespace ml after RollK.
 //
 // Layout as the row-split minibatch step (r16_common.h): one workgroup of 8
 // waves per CU keeps W1 and the head weights in LDS; a wave owns a tile of
@@ -82,7 +82,7 @@ static bool rollout16_eligible(const PolicyK& P, int64_t N, int max_wg, bool bf,
     return rollout16_shape(P, bf, rnn) && max_wg == 0 && rollout16_waves(N) > 0;
 }
 // A population's rollouts on the row-split kernel (rollout16_pop_kernel,
-// policy.hip): every policy of that shape (mlearn_policy_pop_prepare checks
+// policy_rollout.h): every policy of that shape (mlearn_policy_pop_prepare checks
 // they agree), uncapped, N a multiple of 128 (so the 8 waves of a workgroup
 // hold tiles of one policy in every round) and every wave of the chip with a
 // tile (>= 2 048 16-env tiles in all).

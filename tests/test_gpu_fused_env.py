@@ -16,7 +16,7 @@ pytestmark = pytest.mark.gpu
 BUCKETS = [4, 8, 5, 5, 2, 2]
 
 
-def _manager(gpu, fused, dtype, N, H, mb, P=1, lstm=False, use_graph=False):
+def _manager(gpu, fused, dtype, N, H, mb, P=1, lstm=False, use_graph=False, chunks=1):
     import madrona_learn as ml
     from madrona_learn.envs import DummyVecEnv
     from tests.test_gpu_train import make_policy
@@ -31,7 +31,7 @@ def _manager(gpu, fused, dtype, N, H, mb, P=1, lstm=False, use_graph=False):
         lr=3e-4, algo=ml.PPOConfig(num_epochs=2, minibatch_size=mb, clip_coef=0.2,
                                    value_loss_coef=0.5, entropy_coef={"actions": 0.01},
                                    max_grad_norm=0.5),
-        num_bptt_chunks=1, gamma=0.99, gae_lambda=0.95, seed=11, metrics_buffer_size=4,
+        num_bptt_chunks=chunks, gamma=0.99, gae_lambda=0.95, seed=11, metrics_buffer_size=4,
         dreamer_v3_critic=False, compute_dtype=dtype, pbt=pbt)
     if lstm:
         from tests.test_gpu_lstm import make_actor_critic
@@ -44,16 +44,25 @@ def _manager(gpu, fused, dtype, N, H, mb, P=1, lstm=False, use_graph=False):
     return env, ml.init_training(gpu, cfg, fns, pol, use_graph=use_graph)
 
 
+def _case(i, dtype, N, H, mb, P, lstm, graph, chunks=1):
+    # (the id pytest gave the row before `chunks` joined it; 2 chunks say so)
+    name = f"dtype{i}-{N}-{H}-{mb}-{P}-{lstm}-{graph}" + ("" if chunks == 1 else f"-{chunks}chunks")
+    return pytest.param(dtype, N, H, mb, P, lstm, graph, chunks, id=name)
+
+
 @pytest.mark.parametrize("mode", ["one_launch", "multi_tile", "c_per_step", "py_per_step"])
-@pytest.mark.parametrize("dtype,N,H,mb,P,lstm,graph", [
-    (torch.float32, 80, 64, 16, 1, False, False),    # partial last workgroup (80 = 2.5 x 32)
-    (torch.bfloat16, 1024, 256, 256, 1, False, True),
-    (torch.float32, 128, 64, 16, 2, False, True),     # population: one launch for both policies
-    (torch.bfloat16, 384, 256, 32, 3, False, True),   # 3 policies x 4 tiles in one launch
-    (torch.float32, 128, 64, 32, 2, True, True),      # population of LSTM policies
-    (torch.bfloat16, 128, 256, 32, 1, True, False),   # LSTM H = 256: carry, start states, clears
-    (torch.float32, 64, 64, 32, 1, True, False)])     # LSTM carry + done clears
-def test_fused_env_step_is_bit_identical(gpu, mode, dtype, N, H, mb, P, lstm, graph):
+@pytest.mark.parametrize("dtype,N,H,mb,P,lstm,graph,chunks", [
+    _case(0, torch.float32, 80, 64, 16, 1, False, False),    # partial last workgroup (80 = 2.5 x 32)
+    _case(1, torch.bfloat16, 1024, 256, 256, 1, False, True),
+    _case(2, torch.float32, 128, 64, 16, 2, False, True),     # population: one launch for both policies
+    _case(3, torch.bfloat16, 384, 256, 32, 3, False, True),   # 3 policies x 4 tiles in one launch
+    _case(4, torch.float32, 128, 64, 32, 2, True, True),      # population of LSTM policies
+    _case(5, torch.bfloat16, 128, 256, 32, 1, True, False),   # LSTM H = 256: carry, start states, clears
+    _case(6, torch.float32, 64, 64, 32, 1, True, False),      # LSTM carry + done clears
+    # 2 bptt chunks of 16 steps on a partial last tile: the start-state writes at t = 16
+    # (minibatch 32: the recurrent update takes multiples of 32 sequences)
+    _case(7, torch.float32, 80, 64, 32, 1, True, False, chunks=2)])
+def test_fused_env_step_is_bit_identical(gpu, mode, dtype, N, H, mb, P, lstm, graph, chunks):
     """one_launch: the whole rollout + bootstrap in one launch
     (mlearn_policy_rollout_env, one workgroup per env tile here; a
     population: mlearn_policy_rollout_env_pop over every policy's tiles);
@@ -65,11 +74,14 @@ def test_fused_env_step_is_bit_identical(gpu, mode, dtype, N, H, mb, P, lstm, gr
     each workgroup, which restages the parameters when its next tile belongs
     to another policy (config P's 2048 tiles on 768 slots take that branch);
     c_per_step: the same entry's per-step launches (max_workgroups = -1);
-    py_per_step: one rollout_step_env call per step from the host."""
+    py_per_step: one rollout_step_env call per step from the host.
+
+    The row with 2 bptt chunks (T = 32: 16 steps each) compares the in-kernel
+    and the host per-step derivation of the start-state writes at t = 16."""
     from madrona_learn import _native as nat
     from madrona_learn.rollouts import RolloutManager
-    env_a, a = _manager(gpu, True, dtype, N, H, mb, P, lstm, graph)
-    env_b, b = _manager(gpu, False, dtype, N, H, mb, P, lstm, graph)
+    env_a, a = _manager(gpu, True, dtype, N, H, mb, P, lstm, graph, chunks)
+    env_b, b = _manager(gpu, False, dtype, N, H, mb, P, lstm, graph, chunks)
     rm = a.rollout_mgr
     rm.whole_rollout = mode != "py_per_step"
     tiles = (rm.B + 31) // 32
