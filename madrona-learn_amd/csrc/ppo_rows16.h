@@ -197,6 +197,18 @@ __device__ inline void r16_ln_bwd(f32x4 (&acc)[kR16NB], uint32_t (&zw)[kR16NB][2
     } while (0)
 #endif
 
+// One tile's inputs from the store, as loaded (15 registers): the X_0 row
+// chunks of the first layer's B operand (natural k order) and this lane's
+// first two loss tasks (row r, group (lane + 64u) >> 4; group K = the value).
+// Carried across the tile loop: a tile's set is loaded while the tile before
+// it runs (tile 0's ahead of the prologue).
+template <int DS> struct R16In {
+    bf16x8 xf[DS];
+    float adv, rv, vv;
+    int act[2];
+    float lp[2];
+};
+
 // NW waves per workgroup (8: two per SIMD; 4 or 2: one per SIMD), NT 16-row
 // tiles per wave (rows16_cfg).
 template <bool METRICS, int NW, int NT, int HC>
@@ -220,47 +232,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
     const int K = P.K;
     constexpr int D = kR16D, DS = D / 32;  // the first layer's k-steps
 
-    // ---- prologue: W1 and head images (P.wt[1], P.head_t: fragment order,
-    // permuted k, K = 256) re-laid as [out row][512 B] with swizzled 8-byte
-    // units; LayerNorm scale / bias, head bias, the loss tasks' group tables
-    {
-        static_assert(NW == kR16Waves, "r16_stage stages with kR16Waves waves");
-        r16_stage<HC>(P, smem, tid);
-        int* tab = (int*)(smem + LY::OffTab);
-        if (tid <= MLEARN_MAX_GROUPS) {
-            tab[tid] = P.off[tid];
-            ((float*)tab)[MLEARN_MAX_GROUPS + 1 + tid] = tid < MLEARN_MAX_GROUPS ? hp.ecoef[tid] : 0.f;
-            ((float*)tab)[2 * (MLEARN_MAX_GROUPS + 1) + tid] =
-                tid < MLEARN_MAX_GROUPS ? hp.objw[tid] : 0.f;
-        }
-    }
-    __syncthreads();
-#ifdef ML_STAMPS
-    const uint64_t r16_t_pro = __builtin_amdgcn_s_memtime();
-#endif
-    const int* t_off = (const int*)(smem + LY::OffTab);
-    const float* t_ec = (const float*)t_off + MLEARN_MAX_GROUPS + 1;
-    const float* t_ow = t_ec + MLEARN_MAX_GROUPS + 1;
-
     // this wave's index: rows [16 NT ptile, 16 NT (ptile + 1)), loss-partials
     // row ptile (32 rows at NT = 2 = a ppo_step tile; 16 rows at NT = 1, WsK::nlp)
     const int ptile = (int)blockIdx.x * NW + wave;
-    const float as0 = adv_st[0], as1 = adv_st[1];
-    // value normaliser values, loaded once (a load in the loss loop waits on
-    // the tile's stores)
-    VnVals vn{hp.norm_vals != 0, {0.f, 0.f, 0.f, 0.f}};
-    if (hp.norm_vals)
-        for (int i = 0; i < 4; ++i) vn.v[i] = adv_st[2 + i];
-    LossAcc m;
-    bool did = false;
-    uint32_t dz0w[kR16NB][2];            // layer-0 dZ of the previous tile (stored late)
-    float cb0[4], cg0[4];                // its layer-0 column partials (stored with it)
-    float* prev_cp = nullptr;
-    int64_t prev_row = -1;
-    const int ntask = 16 * (K + 1);
-    // minibatch row -> (time step, sequence slot); the slot's sequence id is
-    // loaded one tile ahead (issued before, and waited on before, the tile's
-    // stores: a load issued behind stores waits for them, vmcnt being in order)
+    // minibatch row -> (time step, sequence slot)
     auto slot_of = [&](int64_t rw, uint32_t& tl) {
         const uint32_t f = (uint32_t)rw;
         tl = r16_udiv(f, dv.mb_mag, dv.mb_sh);
@@ -274,12 +249,105 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         const uint32_t c = r16_udiv(seq, dv.n_mag, dv.n_sh), b = seq - c * (uint32_t)ro.N;
         return rw < M ? ((int64_t)c * ro.bptt + tl) * ro.ld + b : 0;
     };
-    int64_t sr_n;  // store row of this lane's row in the next tile
+    // a tile's inputs (R16In) from store row sr: raw, straight-line loads from
+    // valid addresses (sr = 0 on padding rows), combined after the tile's
+    // first layer (a branch or an early use would wait on whatever stores
+    // are in flight, vmcnt being in order)
+    const bool has_ret = ro.ret != nullptr, has_val = ro.values != nullptr;
+    auto load_in = [&](int64_t sr, int ln, R16In<DS>& in) {
+        const bf16* orow = (const bf16*)ro.obs + sr * D;
+#pragma unroll
+        for (int s = 0; s < DS; ++s)
+            in.xf[s] = *(const bf16x8*)(orow + 32 * s + 8 * (ln >> 4));
+        in.adv = ro.adv[sr];
+        in.rv = (has_ret ? ro.ret : ro.adv)[sr];
+        in.vv = (has_val ? ro.values : ro.adv)[sr];
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const int grp = (ln + 64 * u) >> 4;
+            const int ga = grp < K ? grp : K - 1;
+            in.act[u] = ro.actions[sr * K + ga];
+            in.lp[u] = ro.logp[sr * K + ga];
+        }
+    };
+    // ---- prologue: tile 0's inputs, and W1 and head images (P.wt[1],
+    // P.head_t: fragment order, permuted k, K = 256) re-laid as [out row]
+    // [512 B] with swizzled 8-byte units; LayerNorm scale / bias, head bias,
+    // the loss tasks' group tables.  Two memory round trips, not four: the
+    // wave's mb_seq entry is loaded first and the images' loads are issued
+    // behind it; the gather that entry addresses (128-byte rows out of the
+    // whole store) is issued as soon as it lands -- the oldest load, so a
+    // counted wait leaves the images' loads in flight -- and is itself in
+    // flight under the LDS writes and the barrier (the writes wait for the
+    // images' loads alone, the gather being younger).  Tile 0 takes its wait.
+    static_assert(NW == kR16Waves, "R16Stage stages with kR16Waves waves");
+    R16In<DS> in;
     {
         uint32_t tl;
         const int64_t rw = (int64_t)ptile * (16 * NT) + (tid & 15);
-        sr_n = srow_of(rw, (uint32_t)mb_seq[slot_of(rw, tl)]);
+        R16Stage<HC> stg;
+        int tb_off = 0;  // this thread's entries of the group tables
+        float tb_ec = 0.f, tb_ow = 0.f;
+#ifdef ML_R16_GATHER_FIRST  // (A/B build: the gather ahead of every staging load)
+        load_in(srow_of(rw, (uint32_t)mb_seq[slot_of(rw, tl)]), tid & 63, in);
+#else
+        const uint32_t seq0 = (uint32_t)mb_seq[slot_of(rw, tl)];
+#endif
+        __builtin_amdgcn_sched_barrier(0);
+        // (everything written to LDS below is loaded ahead of the gather: a
+        // wait for a load issued behind it would wait for the gather too)
+        if (tid <= MLEARN_MAX_GROUPS) {
+            tb_off = P.off[tid];
+            tb_ec = tid < MLEARN_MAX_GROUPS ? hp.ecoef[tid] : 0.f;
+            tb_ow = tid < MLEARN_MAX_GROUPS ? hp.objw[tid] : 0.f;
+        }
+        stg.load_params(P, tid);
+        stg.load_images(P, tid);
+#ifndef ML_R16_GATHER_FIRST
+        __builtin_amdgcn_sched_barrier(0);
+        load_in(srow_of(rw, r16_late(seq0)), tid & 63, in);
+        __builtin_amdgcn_sched_barrier(0);
+#endif
+        stg.put(P, smem, tid);
+        int* tab = (int*)(smem + LY::OffTab);
+        if (tid <= MLEARN_MAX_GROUPS) {
+            tab[tid] = tb_off;
+            ((float*)tab)[MLEARN_MAX_GROUPS + 1 + tid] = tb_ec;
+            ((float*)tab)[2 * (MLEARN_MAX_GROUPS + 1) + tid] = tb_ow;
+        }
     }
+    const float as0 = adv_st[0], as1 = adv_st[1];
+    // value normaliser values, loaded once (a load in the loss loop waits on
+    // the tile's stores)
+    VnVals vn{hp.norm_vals != 0, {0.f, 0.f, 0.f, 0.f}};
+    if (hp.norm_vals)
+        for (int i = 0; i < 4; ++i) vn.v[i] = adv_st[2 + i];
+    __syncthreads();
+#ifdef ML_STAMPS
+    const uint64_t r16_t_pro = __builtin_amdgcn_s_memtime();
+#endif
+    const int* t_off = (const int*)(smem + LY::OffTab);
+    const float* t_ec = (const float*)t_off + MLEARN_MAX_GROUPS + 1;
+    const float* t_ow = t_ec + MLEARN_MAX_GROUPS + 1;
+
+    LossAcc m;
+    bool did = false;
+    uint32_t dz0w[kR16NB][2];            // layer-0 dZ of the previous tile (stored late)
+    float cb0[4], cg0[4];                // its layer-0 column partials (stored with it)
+    float* prev_cp = nullptr;
+    int64_t prev_row = -1;
+    const int ntask = 16 * (K + 1);
+    // store row of this lane's row in the next tile: its slot's sequence id
+    // is loaded at the tile's start and consumed before the tile's stores (a
+    // load issued behind stores waits for them, vmcnt being in order)
+    int64_t sr_n = 0;
+    // The loads of tile tt + 1 are issued from inside tile tt, except where
+    // the loss metrics' 18 accumulators are live across the loop: at NT = 2
+    // that instantiation is over the register budget as it is, the 15
+    // carried registers add to its spill from either issue point (18 / 19
+    // VGPRs against 15 with the loads at the tile's start), and its launch
+    // is one of an update's 64.
+    constexpr bool kAhead = !METRICS;
 
 #pragma clang loop unroll(disable)
     for (int tt = 0; tt < NT; ++tt) {
@@ -294,22 +362,38 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         const int64_t row0 = (int64_t)ptile * (16 * NT) + 16 * tt;
         const int64_t row = row0 + r;
         const bool live = row < M;
-        // (sr_n is VALU-written: reading it here needs no vmcnt wait, which the
-        // loop header would otherwise take in full, stores included)
-        const int64_t sr = sr_n;
+        // the tile's inputs, loaded while the tile before ran (tile 0: ahead
+        // of the prologue), through opaque copies: their wait is taken here,
+        // where nothing younger is in flight, not in full at the loop header
+        if (kAhead || tt == 0) {
+#pragma unroll
+            for (int s = 0; s < DS; ++s)
+                in.xf[s] = __builtin_bit_cast(bf16x8, r16_late(__builtin_bit_cast(u4r, in.xf[s])));
+            in.adv = r16_late(in.adv);
+            in.rv = r16_late(in.rv);
+            in.vv = r16_late(in.vv);
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                in.act[u] = r16_late(in.act[u]);
+                in.lp[u] = r16_late(in.lp[u]);
+            }
+        } else {
+            load_in(sr_n, lane, in);  // (no tile-ahead loads in this build: at the tile's start)
+        }
+        bf16x8 xf[DS];
+#pragma unroll
+        for (int s = 0; s < DS; ++s) xf[s] = in.xf[s];
+        float t_adv = in.adv, rv = in.rv, vv = in.vv;
+        int ract[2] = {in.act[0], in.act[1]};
+        float rlp[2] = {in.lp[0], in.lp[1]};
         uint32_t seq_n = 0;
         if (tt + 1 < NT) {
             uint32_t tl;
             seq_n = (uint32_t)mb_seq[slot_of(row + 16, tl)];
         }
-        // ---- layer 0: X_0 rows from the store (natural k order), W_0 from its
+        // ---- layer 0: X_0 rows (natural k order), W_0 from its
         // fragment-order image in L2 (P.wt[0], K = D, natural k): element
         // (n, k = 32s + 8g) at ((n/32 * D/16 + 2s + g/2) * 64 + n%32 + 32(g&1)) * 8
-        bf16x8 xf[DS];
-        const bf16* orow = (const bf16*)ro.obs + sr * D;
-#pragma unroll
-        for (int s = 0; s < DS; ++s)
-            xf[s] = *(const bf16x8*)(orow + 32 * s + 8 * g);  // (padding rows: row 0)
         // (each use of the first layer takes its own opaque copy of the lane: the
         // forward's 16 fragment addresses are otherwise CSE'd into the
         // backward's recompute and held live across the tile)
@@ -323,23 +407,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
                 return *(const bf16x8*)(w0 + idx);
             };
         };
-        // this lane's first two loss tasks (row r, group (lane + 64u) >> 4; group
-        // K = the value): raw inputs loaded here, straight-line from valid
-        // addresses (sr = 0 on padding rows), and combined after the first
-        // layer (a branch or an early use here would wait on the previous
-        // tile's stores, vmcnt being in order)
-        const bool has_ret = ro.ret != nullptr, has_val = ro.values != nullptr;
-        float t_adv = ro.adv[sr];
-        float rv = (has_ret ? ro.ret : ro.adv)[sr], vv = (has_val ? ro.values : ro.adv)[sr];
-        int ract[2];
-        float rlp[2];
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const int grp = (lane + 64 * u) >> 4;
-            const int ga = grp < K ? grp : K - 1;
-            ract[u] = ro.actions[sr * K + ga];
-            rlp[u] = ro.logp[sr * K + ga];
-        }
         auto bf0 = [&](int s) { return xf[s]; };
         // Z_0 (packed) and its statistics stay live to the layer-0 backward
         uint32_t zw0[kR16NB][2], zw[kR16NB][2], aw[kR16NB][2];
@@ -558,6 +625,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         // dZ_1 rows out now, ahead of the W1^T product and the layer-0
         // backward: the next tile's first loads wait for them (vmcnt in order)
         r16_store_rows_keep((bf16*)ws.dz[1] + r16_late(row) * kR16H, dzw, g);
+        // the next tile's inputs: issued here, behind the tile's last operand
+        // stores, with the W1^T product and the layer-0 backward (LDS and
+        // registers only) to cover the gather; the store row through an
+        // opaque copy, so the eight addresses are formed here and not held
+        // from the end of layer 0.  The last tile issues nothing.
+#ifndef ML_R16_AHEAD_LATE
+        if (kAhead && tt + 1 < NT) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_in(r16_late(sr_n), lane, in);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            in = R16In<DS>{};  // (dead: otherwise tile tt's set stays live to the loop's end)
+        }
+#endif
         R16_STAMP(8);
         f32x4 acc[kR16NB];
 #pragma unroll
@@ -569,6 +650,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
             },
             [&](int s) { return r16_bfrag(dzw, s); });
         R16_STAMP(9);
+#ifdef ML_R16_AHEAD_LATE  // (A/B build: the issue point behind the W1^T product)
+        if (kAhead && tt + 1 < NT) {
+            __builtin_amdgcn_sched_barrier(0);
+            load_in(r16_late(sr_n), lane, in);
+            __builtin_amdgcn_sched_barrier(0);
+        } else {
+            in = R16In<DS>{};  // (dead: otherwise tile tt's set stays live to the loop's end)
+        }
+#endif
         R16_STAMP(10);
         // ---- layer 0 LayerNorm / ReLU backward
         R16_STAMP(11);

@@ -326,50 +326,62 @@ __device__ inline uint32_t r16_udiv(uint32_t n, uint32_t mag, int sh) {
 // threads of the 8-wave workgroup; the caller's barrier orders it): W1 and
 // head images (P.wt[1], P.head_t: fragment order, permuted k, K = 256)
 // re-laid as [out row][512 B] with swizzled 8-byte units, LayerNorm scale /
-// bias of both layers, head bias.
-template <int HC = kR16HC>
-__device__ inline void r16_stage(const PolicyK& P, char* smem, int tid) {
+// bias of both layers, head bias.  In two halves, the global loads (images,
+// then parameters) and the LDS writes, so that a caller can issue loads of
+// its own between them: r16_stage runs them back to back.
+template <int HC = kR16HC> struct R16Stage {
     typedef R16Lay<HC> LY;
-    char* w1img = smem + LY::OffW1;
-    char* whimg = smem + LY::OffWh;
-    float* gb = (float*)(smem + LY::OffGb);
-    float* hb = (float*)(smem + LY::OffHb);
-    {
+    static constexpr int N1 = kR16H * kR16H * 2 / 16 / (64 * kR16Waves);  // 16 per thread
+    u4r v1[N1], vh[2];
+    float pv[2], hbv;
+    __device__ inline void load_images(const PolicyK& P, int tid) {
         const u4r* src1 = (const u4r*)P.wt[1];
         const u4r* srch = (const u4r*)P.head_t;
-        constexpr int N1 = kR16H * kR16H * 2 / 16 / (64 * kR16Waves);  // 16 per thread
-        u4r v1[N1], vh[2];
 #pragma unroll
         for (int i = 0; i < N1; ++i) v1[i] = src1[tid + i * 64 * kR16Waves];
         if (HC == 32)
 #pragma unroll
             for (int i = 0; i < 2; ++i) vh[i] = srch[tid + i * 64 * kR16Waves];
-        float pv[2];
+    }
+    __device__ inline void load_params(const PolicyK& P, int tid) {
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int j = tid + i * 64 * kR16Waves, l = j >> 9, c = j & 511;
             pv[i] = c < kR16H ? P.lns[l][c] : P.lnb[l][c - kR16H];
         }
-        const float hbv = tid < HC ? P.head_b[tid] : 0.f;
+        hbv = tid < HC ? P.head_b[tid] : 0.f;
+    }
+    __device__ inline void put(const PolicyK& P, char* smem, int tid) const {
+        char* w1img = smem + LY::OffW1;
+        char* whimg = smem + LY::OffWh;
+        float* gb = (float*)(smem + LY::OffGb);
+        float* hb = (float*)(smem + LY::OffHb);
         // 16-byte unit U of a (K = 256, perm) image: n = ((U >> 10) << 5) | (U & 31),
         // h = (U >> 5) & 1, s16 = (U >> 6) & 15; its halves hold inputs
         // 16 s16 + 4h .. +3 and 16 s16 + 8 + 4h .. +3 (units 4 s16 + h, 4 s16 + 2 + h)
-        auto put = [&](char* img, int U, u4r v) {
+        auto put1 = [&](char* img, int U, u4r v) {
             const int n = ((U >> 10) << 5) | (U & 31), h = (U >> 5) & 1, s16 = (U >> 6) & 15;
             *(u2r*)(img + r16_off(n, 4 * s16 + h)) = u2r{v[0], v[1]};
             *(u2r*)(img + r16_off(n, 4 * s16 + 2 + h)) = u2r{v[2], v[3]};
         };
 #pragma unroll
-        for (int i = 0; i < N1; ++i) put(w1img, tid + i * 64 * kR16Waves, v1[i]);
+        for (int i = 0; i < N1; ++i) put1(w1img, tid + i * 64 * kR16Waves, v1[i]);
         if (HC == 32)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) put(whimg, tid + i * 64 * kR16Waves, vh[i]);
+            for (int i = 0; i < 2; ++i) put1(whimg, tid + i * 64 * kR16Waves, vh[i]);
 #pragma unroll
         for (int i = 0; i < 2; ++i) gb[tid + i * 64 * kR16Waves] = pv[i];
         if (tid < HC) hb[tid] = hbv;
         if (HC != 32 && tid < P.CB)  // the two-hot critic's bin values (dists.py:128-141)
             ((float*)(smem + LY::OffBins))[tid] = twohot_bin(tid, P.CB);
     }
+};
+template <int HC = kR16HC>
+__device__ inline void r16_stage(const PolicyK& P, char* smem, int tid) {
+    R16Stage<HC> st;
+    st.load_images(P, tid);
+    st.load_params(P, tid);
+    st.put(P, smem, tid);
 }
 
 // A fragment of the head's forward product (M = head column n, the k order of

@@ -46,6 +46,14 @@ print("per wave (cycles, median / max): prologue", np.median(w0[:, 14] - w0[:, 1
       "| epilogue (last stores done)", np.median(w0[:, 15] - st[1::2, 12]),
       (w0[:, 15] - st[1::2, 12]).max(), "| entry..end", np.median(w0[:, 15] - w0[:, 13]),
       (w0[:, 15] - w0[:, 13]).max())
+# the head of the launch: kernel entry to the end of tile 0's first layer
+# (staging, barrier, the wave's mb_seq entry, the gather, 32 MFMAs), and the
+# same phase of the last tile, which has no prologue in front of it
+h0 = w0[:, 1] - w0[:, 13]
+l0n = st[1::2, 1] - st[1::2, 0]
+print("tile 0 kernel entry -> end of layer 0 (median / mean / max):", np.median(h0),
+      float(h0.mean()), h0.max(), "| of which after the prologue", np.median(w0[:, 1] - w0[:, 14]),
+      "| last tile's layer 0", np.median(l0n), float(l0n.mean()), l0n.max())
 # per workgroup (8 waves, one CU): wave time entry..end by wave index, and the
 # spread inside a workgroup vs across workgroups
 tw = (w0[:, 15] - w0[:, 13]).reshape(-1, 8)
