@@ -299,7 +299,8 @@ __device__ inline void loss_group_fixed(const HpK& hp, S* lg, int nb, int a, flo
     }
 }
 
-// Any group size (<= 31): three passes over the logits in LDS.
+// Any group size (tested to 33 logits; validate_policy bounds it by the head
+// width): at most 8 in registers, above that three passes over the logits in LDS.
 template <typename S>
 __device__ inline void loss_group(const HpK& hp, S* lg, int nb, int a, float old_lp, float adv,
                                   float ecoef, float objw, LossAcc& m) {

@@ -9,6 +9,9 @@ may legitimately go either way.  Per action group:
   3. on the remaining rows the action is the oracle's top-1 or top-2 index;
   4. at most 2 * margin * rows + 5 rows remain.
 
+A group of one logit has no runner-up: every row is clear (gap = +inf) and
+the only admissible action is 0.
+
 (4) is a condition on the inputs, not on the kernel: the gap between the two
 largest of independent Gumbel-perturbed logits has density at most 1 at zero,
 so the expected share of unclear rows is at most `margin`; twice that plus 5
@@ -39,7 +42,10 @@ def check_actions(noisy, got, buckets, margin, tag=""):
         rest = sl.copy()
         rest[np.arange(rows), top1] = -np.inf
         top2 = np.argmax(rest, -1)
-        gap = sl[np.arange(rows), top1] - sl[np.arange(rows), top2]
+        if nb == 1:  # no runner-up: the row is clear and the action is 0
+            gap = np.full(rows, np.inf)
+        else:
+            gap = sl[np.arange(rows), top1] - sl[np.arange(rows), top2]
         clear = gap > margin
         assert np.array_equal(a[clear], top1[clear]), (tag, g, np.flatnonzero(a != top1)[:8])
         near = ~clear

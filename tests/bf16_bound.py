@@ -30,7 +30,11 @@ test_minibatch_grad 0.10 (W1 at D=256, H=256, L=4), test_lstm_minibatch_grad
 0.13 (head_W at D=64, H=256, L=2), test_minibatch_grad_b1_size 0.02,
 test_row_split_step_kernel 0.04 row split / 0.05 feature split (W0 at 1023 x
 32), its two-hot form 0.006, test_value_loss_variants 0.001: the kernels sit
-8x or more inside factor = 1.0."""
+8x or more inside factor = 1.0.  Under the other action layouts
+(tests/test_gpu_action_layouts.py) the largest was 0.08
+(test_row_split_step_layouts[one31-1-1024], ln_scale0, the same on both step
+kernels), then 0.05 (test_lstm_minibatch_grad_layouts, test_minibatch_grad_layouts
+one3 at D=48, H=128, L=3); every other layout's feed-forward gradient 0.007 or less."""
 
 import json
 import os
@@ -118,7 +122,16 @@ def check_bf16_mean(name, got, x_bf16, x_f32, rel_floor=1e-5):
 
 def loss_rows(met, hp):
     """Per-row PPO loss of the oracle's metrics dict (ppo.py:221-262): its mean
-    over the rows is the loss."""
-    return (-np.asarray(met["Action Obj"], np.float64).mean(-1)
-            + hp["value_loss_coef"] * np.asarray(met["Value Loss"], np.float64)
-            - hp["entropy_coef"] * np.asarray(met["Entropy"], np.float64).mean(-1))
+    over the rows is the loss.  With hp["action_groups"] = [(n_key, coef), ...]
+    each key's surrogate and entropy are means over its own sub-actions, summed
+    over the keys (ppo.py:221-239)."""
+    obj = np.asarray(met["Action Obj"], np.float64)
+    ent = np.asarray(met["Entropy"], np.float64)
+    groups = hp.get("action_groups") or [(obj.shape[-1], hp["entropy_coef"])]
+    assert sum(n for n, _ in groups) == obj.shape[-1]
+    rows = hp["value_loss_coef"] * np.asarray(met["Value Loss"], np.float64)
+    j = 0
+    for n_key, coef in groups:
+        rows = rows - obj[..., j:j + n_key].mean(-1) - coef * ent[..., j:j + n_key].mean(-1)
+        j += n_key
+    return rows

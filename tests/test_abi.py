@@ -217,3 +217,79 @@ def test_two_hot_critic_layout_and_head_width():
     arch = compile_arch(ac, 64, torch.bfloat16)
     assert arch.critic_bins == 63 and arch.head_cols == 96
     assert param_layout(arch)["total"] == ref.param_layout(64, 256, 2, 26, 63)["total"]
+
+
+def _layout_desc(buckets, bins=1, dtype=None, H=256, layers=2, D=64):
+    from madrona_learn import _native as nat
+    d = nat.MlpPolicy()
+    d.dtype = nat.DTYPE_BF16 if dtype is None else dtype
+    d.obs_dim, d.hidden, d.num_layers = D, H, layers
+    d.critic_bins = bins
+    d.actions = nat.action_layout(list(buckets))
+    for l in range(layers):
+        d.w_t[l] = d.ln_scale[l] = d.ln_bias[l] = 1
+        d.w[l] = 1
+    d.head_t = d.head = d.head_bias = 1
+    return d
+
+
+def test_action_layouts_param_count_and_head_width():
+    """Every layout of tests/action_layouts.py: the parameter count is the
+    oracle's layout total, the head 32 columns for A + CB <= 32 and 96 above."""
+    from madrona_learn import _native as nat
+    from oracle import ppo_ref as ref
+    from tests.action_layouts import LAYOUT_CRITICS, LAYOUTS
+    L = nat.lib()
+    wide = {("k16wide", 1), ("wide33", 63), ("k16", 63)}
+    for name, cb in LAYOUT_CRITICS:
+        b = LAYOUTS[name]
+        for H, layers, D in ((256, 2, 64), (64, 1, 16), (128, 3, 48)):
+            d = _layout_desc(b, cb, H=H, layers=layers, D=D)
+            assert L.mlearn_param_count(ctypes.byref(d)) == \
+                ref.param_layout(D, H, layers, sum(b), cb)["total"], (name, cb, H)
+        hc = 96 if (name, cb) in wide else 32
+        assert (sum(b) + cb > 32) == (hc == 96)
+        assert L.mlearn_head_cols(ctypes.byref(d)) == hc == nat.head_cols(sum(b), cb), (name, cb)
+
+
+def test_action_layouts_kernel_selection():
+    """The row-split step takes at most 7 groups under either head (k7, one3,
+    wide33 with 63 bins), not 8 groups (k8) nor a scalar critic under the
+    96-column head (k16wide); the row-split rollout takes 8 groups, not 9
+    (without a device the library assumes 256 CUs: 32,768 envs)."""
+    from madrona_learn import _native as nat
+    from tests.action_layouts import LAYOUTS
+    L = nat.lib()
+    sel = lambda d, M, req=0: L.mlearn_ppo_step_kernel(ctypes.byref(d), M, req)  # noqa: E731
+    for rows in (32768, 65536):
+        for name, cb in (("k7", 1), ("one3", 1), ("wide33", 63)):
+            d = _layout_desc(LAYOUTS[name], cb)
+            assert sel(d, rows) == 2 and sel(d, rows, 2) == 2 and sel(d, rows, 1) == 1, (name, rows)
+        for name in ("k8", "k16wide"):
+            d = _layout_desc(LAYOUTS[name])
+            assert sel(d, rows) == 1 and sel(d, rows, 1) == 1, (name, rows)
+            assert sel(d, rows, 2) == -1, (name, rows)
+    rk = lambda d, N, req=0: L.mlearn_policy_rollout_kernel(ctypes.byref(d), None, N, 0, req)  # noqa: E731
+    assert rk(_layout_desc(LAYOUTS["k8"]), 32768) == 2
+    assert rk(_layout_desc(LAYOUTS["one3"]), 32768) == 2
+    nine = _layout_desc([3] * 9)
+    assert rk(nine, 32768) == 1 and rk(nine, 32768, 2) == -1
+
+
+def test_standalone_sampler_rejects_32_logits():
+    """check_layout (mlearn_discrete_sample_f32 / mlearn_action_stats_f32: a
+    group's logits are held in 32 registers) admits A <= 31 and rejects A = 32
+    with a message, before any pointer is looked at."""
+    from madrona_learn import _native as nat
+    L = nat.lib()
+    lay = nat.action_layout([2] * 16)
+    assert lay.num_logits == 32
+    msg = _einval(L.mlearn_discrete_sample_f32(None, 32, lay, 8, 1, 2, None, 0, 0, 1, None, None,
+                                               None))
+    assert "A=32" in msg, msg
+    msg = _einval(L.mlearn_action_stats_f32(None, 32, lay, 8, None, None, None, None))
+    assert "A=32" in msg, msg
+    # A = 31 passes the layout check (the call then fails on its null pointers)
+    msg = _einval(L.mlearn_discrete_sample_f32(None, 31, nat.action_layout([31]), 8, 1, 2, None, 0,
+                                               0, 1, None, None, None))
+    assert "null pointer" in msg, msg

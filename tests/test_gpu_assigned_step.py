@@ -15,6 +15,7 @@ import torch
 
 from oracle import ppo_ref as ref
 from tests.action_check import check_actions
+from tests.action_layouts import LAYOUTS
 from tests.test_gpu_policy import BUCKETS, make_critic, oracle_layout, perturb
 
 pytestmark = pytest.mark.gpu
@@ -29,6 +30,9 @@ CASES = {
     "bf16_h128_twohot": (torch.bfloat16, 48, 128, 3, 63, False),  # the 96-column head
     "bf16_h256_ema": (torch.bfloat16, 64, 256, 2, 1, True),
 }
+# a case under another action layout (tests/action_layouts.py): 16 groups, so the
+# gathered step's (row, group) task loop takes several passes and writes n * K + g
+LAYOUT_CASES = {"bf16_h256_k16": (torch.bfloat16, 64, 256, 2, 1, False, LAYOUTS["k16"])}
 PATTERNS = ["random", "all_policy_1", "five_rows", "runs_37", "n_31"]
 SENTINEL_A, SENTINEL_F = -77, -12345.0
 
@@ -36,13 +40,19 @@ _setups = {}
 _oracles = {}
 
 
-def make_state(gpu, D, H, L, dtype, seed, CB, ema):
+def _case(case):
+    """(dtype, obs, hidden, layers, critic bins, ema, buckets) of a case name."""
+    c = CASES[case] if case in CASES else LAYOUT_CASES[case]
+    return c if len(c) == 7 else c + (BUCKETS,)
+
+
+def make_state(gpu, D, H, L, dtype, seed, CB, ema, buckets=BUCKETS):
     import madrona_learn as ml
     from madrona_learn.models import MLP, DenseLayerDiscreteActor
     from madrona_learn.train_state import PolicyState, compile_arch
     ac = ml.ActorCritic(
         backbone=ml.BackboneShared(encoder=ml.BackboneEncoder(net=MLP(H, L, dtype))),
-        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(BUCKETS), dtype),
+        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(list(buckets)), dtype),
         critic=make_critic(CB, dtype))
     pre = ml.ObservationsEMANormalizer.create(0.99, dtype) if ema else None
     return PolicyState(ac, compile_arch(ac, D, dtype), pre, gpu, np.random.default_rng(seed))
@@ -51,10 +61,10 @@ def make_state(gpu, D, H, L, dtype, seed, CB, ema):
 def setup(gpu, case):
     """P perturbed policies of different seeds + the observations (built once)."""
     if case not in _setups:
-        dtype, D, H, L, CB, ema = CASES[case]
+        dtype, D, H, L, CB, ema, buckets = _case(case)
         states = []
         for p in range(P):
-            ps = make_state(gpu, D, H, L, dtype, 11 + p, CB, ema)
+            ps = make_state(gpu, D, H, L, dtype, 11 + p, CB, ema, buckets)
             perturb(ps, 100 + p)
             if ema:
                 rng = np.random.default_rng(200 + p)
@@ -74,7 +84,7 @@ def full_runs(gpu, case, n, sample):
     k = (case, n, sample)
     if k not in _oracles:
         states, obs, ctr = setup(gpu, case)
-        K = len(BUCKETS)
+        K = len(_case(case)[6])
         acts = torch.zeros((P, n, K), dtype=torch.int32, device=gpu)
         logp = torch.zeros((P, n, K), dtype=torch.float32, device=gpu) if sample else None
         vals = torch.zeros((P, n), dtype=torch.float32, device=gpu)
@@ -125,7 +135,7 @@ def select(full, a, keep=None):
 def run_assigned(gpu, case, a, sample, with_logp=True):
     from madrona_learn.train_state import AssignedPolicyStep
     states, obs, ctr = setup(gpu, case)
-    n, K = a.shape[0], len(BUCKETS)
+    n, K = a.shape[0], len(_case(case)[6])
     stepper = AssignedPolicyStep(states, n)
     asg = torch.from_numpy(a).to(gpu)
     acts = torch.full((n, K), SENTINEL_A, dtype=torch.int32, device=gpu)
@@ -150,6 +160,25 @@ def test_bit_identity_sampled(gpu, case, pat):
     if pat == "random":
         full = full_runs(gpu, case, a.shape[0], True)
         assert all(not torch.equal(full[2][p], ev) for p in range(P))
+
+
+@pytest.mark.parametrize("case", list(LAYOUT_CASES))
+def test_bit_identity_sampled_layouts(gpu, case):
+    """The sampled bit identity under another action layout, and against the
+    layout's bounds: every action inside its group, a one-logit group's action
+    0 and log-prob exactly 0."""
+    a = pattern("random")
+    full = full_runs(gpu, case, a.shape[0], True)
+    ea, el, ev = select(full, a)
+    acts, logp, vals = run_assigned(gpu, case, a, True)
+    assert torch.equal(acts, ea)
+    assert torch.equal(logp, el)
+    assert torch.equal(vals, ev)
+    assert all(not torch.equal(full[2][p], ev) for p in range(P))
+    for g, nb in enumerate(_case(case)[6]):
+        assert ((acts[:, g] >= 0) & (acts[:, g] < nb)).all()
+        if nb == 1:
+            assert not acts[:, g].any() and not logp[:, g].any()
 
 
 @pytest.mark.parametrize("pat", PATTERNS)

@@ -392,20 +392,21 @@ def test_row_split_rollout_rank_sizes(gpu, N):
     _replay_windows(mgr, env, cfg, [0, N // 2 + 32 * 5, N - 32])
 
 
-def _replay_windows(mgr, env, cfg, windows, critic_bins=1):
+def _replay_windows(mgr, env, cfg, windows, critic_bins=1, buckets=BUCKETS):
     ps = mgr.state.policy_states
     rm = mgr.rollout_mgr
     p0 = ps.params.cpu().numpy().astype(np.float64)
     mgr.update_iter()
     torch.cuda.synchronize()
     s = rm.store
-    lay = ref.param_layout(D, H, 2, 26, critic_bins)
+    A = int(sum(buckets))
+    lay = ref.param_layout(D, H, 2, A, critic_bins)
     for e0 in windows:
         c = slice(e0, e0 + 32)
         oenv = onat.Env(32, D, env.k0, env.k1, e0)
         oenv.reset()
         acts = s.actions[:, c].cpu().numpy()
-        ro, _ = ref.rollout(p0, lay, oenv, T, BUCKETS, mgr.rollout.prng_key, 0, mode="bf16",
+        ro, _ = ref.rollout(p0, lay, oenv, T, buckets, mgr.rollout.prng_key, 0, mode="bf16",
                             gamma=cfg.gamma, actions_override=acts)
         vsens = None
         if critic_bins > 1:  # 1-ulp sensitivity of the oracle's mean(), every step + bootstrap
@@ -420,10 +421,10 @@ def _replay_windows(mgr, env, cfg, windows, critic_bins=1):
             ulp = np.exp2(np.floor(np.log2(np.maximum(np.abs(crit), 1e-30))) - 7)
             vsens = (pr * np.abs(bins - mean) * ulp).sum(-1).reshape(T + 1, 32)
         _check_store(s, ro, c, vsens)
-        gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, e0, 32, 26)
+        gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, e0, 32, A)
                         for t in range(T)])
         noisy = ro["logits"] + gum
-        check_actions(noisy, acts, BUCKETS, 1e-2, f"window {e0}")
+        check_actions(noisy, acts, buckets, 1e-2, f"window {e0}")
         # the env after the rollout (the row split writes it once, at the end)
         assert np.array_equal(env.obs[c].cpu().numpy(), oenv.obs), e0
         assert np.array_equal(env.state[c].cpu().numpy(), oenv.state), e0

@@ -22,14 +22,15 @@ from tests.test_gpu_policy import BUCKETS, make_policy_state, oracle_layout, per
 pytestmark = pytest.mark.gpu
 
 
-def _minibatch_store(rng, ps, T, N, D, mode, seqs, bptt):
+def _minibatch_store(rng, ps, T, N, D, mode, seqs, bptt, buckets=BUCKETS):
     """[T][N] store whose minibatch rows carry old log-probs / values from the
     oracle forward of the current parameters (+ noise, so ratios != 1);
     every other row is random (never read)."""
+    K = len(buckets)
     obs = ref.rnd(rng.standard_normal((T, N, D), dtype=np.float32), mode).astype(np.float32)
-    acts = np.stack([rng.integers(0, b, (T, N)) for b in BUCKETS], -1).astype(np.int32)
+    acts = np.stack([rng.integers(0, b, (T, N)) for b in buckets], -1).astype(np.int32)
     st = {"obs": obs, "actions": acts,
-          "log_probs": (rng.standard_normal((T, N, 6)) - 2.0).astype(np.float32),
+          "log_probs": (rng.standard_normal((T, N, K)) - 2.0).astype(np.float32),
           "values": rng.standard_normal((T, N)).astype(np.float32),
           "advantages": (rng.standard_normal((T, N)) * 2 + 0.3).astype(np.float32),
           "returns": rng.standard_normal((T, N)).astype(np.float32),
@@ -37,8 +38,8 @@ def _minibatch_store(rng, ps, T, N, D, mode, seqs, bptt):
     rows = ref.minibatch_rows(seqs, N, bptt)
     P = ref.unflatten(ps.params.cpu().numpy(), oracle_layout(ps))
     logits, V, _ = ref.forward(P, obs.reshape(T * N, D)[rows], mode)
-    lp, _ = ref.action_stats(logits, BUCKETS, acts.reshape(T * N, 6)[rows])
-    lpf = st["log_probs"].reshape(T * N, 6)
+    lp, _ = ref.action_stats(logits, buckets, acts.reshape(T * N, K)[rows])
+    lpf = st["log_probs"].reshape(T * N, K)
     # ratio noise kept clear of the clip bounds 1 -/+ 0.2 (|ratio - bound| > 1e-3):
     # the clipped objective's derivative jumps there, and a 1-ulp difference in
     # the new log-prob would move a row across (an O(1/M) jump per row)
@@ -53,10 +54,10 @@ def _minibatch_store(rng, ps, T, N, D, mode, seqs, bptt):
     return st, rows
 
 
-def _device_store(gpu, st, dtype):
+def _device_store(gpu, st, dtype, buckets=BUCKETS):
     from madrona_learn.rollouts import RolloutStore
     T, N, D = st["obs"].shape
-    s = RolloutStore(T, N, D, 6, dtype, gpu)
+    s = RolloutStore(T, N, D, len(buckets), dtype, gpu)
     s.obs.copy_(torch.from_numpy(st["obs"]).to(dtype))
     s.actions.copy_(torch.from_numpy(st["actions"]))
     s.log_probs.copy_(torch.from_numpy(st["log_probs"]))
@@ -66,15 +67,36 @@ def _device_store(gpu, st, dtype):
     return s
 
 
-def _run_grad(gpu, ps, s, seqs, mb, bptt, hpd, stats, step_kernel=0, wgrad_form=0):
+def set_group_coefs(hp, K, entropy_coef, action_groups=None):
+    """mlearn_ppo_hparams' per-sub-action coefficients from the oracle's
+    action_groups = [(n_key, coef), ...] (include/mlearn.h: entropy_coef[j] =
+    c_g K / K_g, obj_weight[j] = K / K_g for the group g holding j); without
+    groups every sub-action takes entropy_coef."""
+    if not action_groups:
+        for j in range(K):
+            hp.entropy_coef[j] = entropy_coef
+        return
+    assert sum(n for n, _ in action_groups) == K
+    j = 0
+    for n_key, coef in action_groups:
+        for _ in range(n_key):
+            hp.entropy_coef[j] = coef * K / n_key
+            hp.obj_weight[j] = K / n_key
+            j += 1
+
+
+def _run_grad(gpu, ps, s, seqs, mb, bptt, hpd, stats, step_kernel=0, wgrad_form=0,
+              buckets=BUCKETS, action_groups=None, loss_scale=1.0):
+    """action_groups (default hpd's): the oracle's [(n_key, coef), ...]."""
     from madrona_learn import _native as nat
     hp = nat.PPOHparams()
     hp.step_kernel = step_kernel
     hp.wgrad_form = wgrad_form
     hp.clip_coef, hp.value_loss_coef = hpd["clip_coef"], hpd["value_loss_coef"]
-    for k in range(6):
-        hp.entropy_coef[k] = hpd["entropy_coef"]
-    hp.normalize_advantages, hp.loss_scale = 1, 1.0
+    set_group_coefs(hp, len(buckets), hpd["entropy_coef"],
+                    action_groups or hpd.get("action_groups"))
+    hp.normalize_advantages = 1 if hpd.get("normalize_advantages", True) else 0
+    hp.loss_scale = loss_scale
     hp.clip_value_loss = 1 if hpd.get("clip_value_loss") else 0
     hp.huber_value_loss = 1 if hpd.get("huber_value_loss") else 0
     st = torch.tensor([stats[0], 1.0 / np.sqrt(max(stats[1], 1e-5))], dtype=torch.float32,
@@ -92,19 +114,19 @@ def _run_grad(gpu, ps, s, seqs, mb, bptt, hpd, stats, step_kernel=0, wgrad_form=
     return grad.cpu().numpy(), out.cpu().numpy()
 
 
-def _oracle_pair(ps, batch, hpd, stats):
+def _oracle_pair(ps, batch, hpd, stats, buckets=BUCKETS):
     """The oracle's bf16 and f32 modes on the same minibatch, parameters and
     advantage statistics: {mode: (loss, flat gradient, metrics, aux)}."""
     lay = oracle_layout(ps)
     P = ref.unflatten(ps.params.cpu().numpy(), lay)
     out = {}
     for mode in ("bf16", "f32"):
-        loss, G, met, aux = ref.ppo_loss_grads(P, batch, hpd, BUCKETS, mode, adv_stats=stats)
+        loss, G, met, aux = ref.ppo_loss_grads(P, batch, hpd, buckets, mode, adv_stats=stats)
         out[mode] = (loss, ref.flatten(G, lay), met, aux)
     return out
 
 
-def _check_bf16(tag, g, o, pair, lay, hpd, M, verr_atol=None, factor=1.0):
+def _check_bf16(tag, g, o, pair, lay, hpd, M, verr_atol=None, factor=1.0, buckets=BUCKETS):
     """A bf16 kernel's gradient, loss and metric means within the distance
     bf16 rounding itself moves the oracle's (verr_atol: the two-hot critic's
     'Value Errors', see test_row_split_step_kernel_twohot)."""
@@ -119,10 +141,10 @@ def _check_bf16(tag, g, o, pair, lay, hpd, M, verr_atol=None, factor=1.0):
     else:
         np.testing.assert_allclose(o[15], np.abs(mb_["Value Errors"]).mean(), rtol=2e-2,
                                    atol=verr_atol)
-    assert o[14] == M and o[24] == M * 6
+    assert o[14] == M and o[24] == M * len(buckets)
 
 
-def _check(mode, g, o, loss, gflat, met, M, full_size=False):
+def _check(mode, g, o, loss, gflat, met, M, full_size=False, buckets=BUCKETS):
     assert mode == "f32"
     scale = np.abs(gflat).max()
     if full_size:
@@ -146,7 +168,7 @@ def _check(mode, g, o, loss, gflat, met, M, full_size=False):
     np.testing.assert_allclose(o[10], met["Value Loss"].mean(), rtol=mtol)
     np.testing.assert_allclose(o[15], np.abs(met["Value Errors"]).mean(), rtol=mtol)
     np.testing.assert_allclose(o[20], met["Entropy"].mean(), rtol=mtol)
-    assert o[14] == M and o[24] == M * 6
+    assert o[14] == M and o[24] == M * len(buckets)
 
 
 def _twohot_value_scale(P, obs):

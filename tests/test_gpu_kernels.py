@@ -12,6 +12,7 @@ import torch
 
 from oracle import native as onat
 from oracle import ppo_ref as ref
+from tests.action_layouts import LAYOUTS as ALL_LAYOUTS
 
 pytestmark = pytest.mark.gpu
 
@@ -127,24 +128,43 @@ def test_zscore(gpu):
     assert np.all(got == 0)
 
 
-@pytest.mark.parametrize("sample", [1, 0])
-def test_discrete_sample_bitexact(gpu, sample):
+# action layouts beyond BUCKETS (tests/test_gpu_action_layouts.py): a single
+# group of 31 logits (the standalone sampler's largest), groups above 8 logits
+# next to a group of one with offsets straddling the Philox quads, 16 groups
+LAYOUTS = {n: ALL_LAYOUTS[n] for n in ("one31", "mixed", "k16")}
+
+
+def _discrete_sample_bitexact(gpu, sample, buckets):
     from madrona_learn.dists import DiscreteActionDistributions, PhiloxKey
     rng = np.random.default_rng(5)
     N = 5000
-    lg = (rng.standard_normal((N, 26)) * 2).astype(np.float32)
+    lg = (rng.standard_normal((N, sum(buckets))) * 2).astype(np.float32)
     lg[:10] = 0.0  # exact ties: first-index argmax when not sampling
-    dist = DiscreteActionDistributions(BUCKETS, torch.from_numpy(lg).to(gpu))
+    dist = DiscreteActionDistributions(buckets, torch.from_numpy(lg).to(gpu))
     key = PhiloxKey(77, 99, step=12345678901, env_offset=17)
     if sample:
         acts, logp = dist.sample(key)
     else:
         acts, logp = dist.best(), None
-    exp = onat.sample(lg, BUCKETS, 77, 99, 12345678901, 17, sample=bool(sample))
+    exp = onat.sample(lg, buckets, 77, 99, 12345678901, 17, sample=bool(sample))
     assert np.array_equal(acts.cpu().numpy(), exp)
     if sample:
-        elogp, _ = ref.action_stats(lg, BUCKETS, exp)
+        elogp, _ = ref.action_stats(lg, buckets, exp)
         np.testing.assert_allclose(logp.cpu().numpy(), elogp, rtol=1e-5, atol=2e-6)
+        for g, nb in enumerate(buckets):
+            if nb == 1:  # a group of one logit: log-prob exactly 0
+                assert not logp[:, g].any()
+
+
+@pytest.mark.parametrize("sample", [1, 0])
+def test_discrete_sample_bitexact(gpu, sample):
+    _discrete_sample_bitexact(gpu, sample, BUCKETS)
+
+
+@pytest.mark.parametrize("sample", [1, 0])
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_discrete_sample_bitexact_layouts(gpu, layout, sample):
+    _discrete_sample_bitexact(gpu, sample, LAYOUTS[layout])
 
 
 def test_sampling_distribution(gpu):
@@ -159,16 +179,28 @@ def test_sampling_distribution(gpu):
     np.testing.assert_allclose(freq, p, atol=4e-3)
 
 
-def test_action_stats(gpu):
+def _action_stats(gpu, buckets):
     from madrona_learn.dists import DiscreteActionDistributions
     rng = np.random.default_rng(6)
-    lg = (rng.standard_normal((777, 26)) * 3).astype(np.float32)
-    acts = np.stack([rng.integers(0, b, 777) for b in BUCKETS], -1).astype(np.int32)
-    dist = DiscreteActionDistributions(BUCKETS, torch.from_numpy(lg).to(gpu))
+    lg = (rng.standard_normal((777, sum(buckets))) * 3).astype(np.float32)
+    acts = np.stack([rng.integers(0, b, 777) for b in buckets], -1).astype(np.int32)
+    dist = DiscreteActionDistributions(buckets, torch.from_numpy(lg).to(gpu))
     lp, ent = dist.action_stats(torch.from_numpy(acts).to(gpu))
-    elp, eent = ref.action_stats(lg, BUCKETS, acts)
+    elp, eent = ref.action_stats(lg, buckets, acts)
     np.testing.assert_allclose(lp.cpu().numpy(), elp, rtol=1e-5, atol=2e-6)
     np.testing.assert_allclose(ent.cpu().numpy(), eent, rtol=1e-5, atol=2e-6)
+    for g, nb in enumerate(buckets):
+        if nb == 1:  # a group of one logit: log-prob and entropy exactly 0
+            assert not lp[:, g].any() and not ent[:, g].any()
+
+
+def test_action_stats(gpu):
+    _action_stats(gpu, BUCKETS)
+
+
+@pytest.mark.parametrize("layout", sorted(LAYOUTS))
+def test_action_stats_layouts(gpu, layout):
+    _action_stats(gpu, LAYOUTS[layout])
 
 
 @pytest.mark.parametrize("n", [1, 16, 1000, 8192, 16384, 100003])

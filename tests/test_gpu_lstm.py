@@ -28,7 +28,7 @@ pytestmark = pytest.mark.gpu
 BUCKETS = [4, 8, 5, 5, 2, 2]
 
 
-def make_actor_critic(hidden, layers, dtype, critic_bins=1):
+def make_actor_critic(hidden, layers, dtype, critic_bins=1, buckets=BUCKETS):
     import madrona_learn as ml
     from madrona_learn.models import MLP, DenseLayerDiscreteActor
     from madrona_learn.rnn import LSTM
@@ -36,13 +36,14 @@ def make_actor_critic(hidden, layers, dtype, critic_bins=1):
     return ml.ActorCritic(
         backbone=ml.BackboneShared(encoder=ml.RecurrentBackboneEncoder(
             net=MLP(hidden, layers, dtype), rnn=LSTM(hidden, 1, dtype))),
-        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(BUCKETS), dtype),
+        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(list(buckets)), dtype),
         critic=make_critic(critic_bins, dtype))
 
 
-def make_policy_state(gpu, obs_dim, hidden, layers, dtype, seed=0, critic_bins=1):
+def make_policy_state(gpu, obs_dim, hidden, layers, dtype, seed=0, critic_bins=1,
+                      buckets=BUCKETS):
     from madrona_learn.train_state import PolicyState, compile_arch
-    ac = make_actor_critic(hidden, layers, dtype, critic_bins)
+    ac = make_actor_critic(hidden, layers, dtype, critic_bins, buckets)
     arch = compile_arch(ac, obs_dim, dtype)
     assert arch.lstm_hidden == hidden
     return PolicyState(ac, arch, None, gpu, np.random.default_rng(seed))
@@ -118,7 +119,12 @@ CRITIC_CASES = [c + (1,) for c in CASES] + [
 
 @pytest.mark.parametrize("mode,dtype,D,H,L,CB", CRITIC_CASES)
 def test_lstm_rollout_step(gpu, mode, dtype, D, H, L, CB):
-    ps = make_policy_state(gpu, D, H, L, dtype, seed=D + H, critic_bins=CB)
+    lstm_rollout_step_case(gpu, mode, dtype, D, H, L, CB)
+
+
+def lstm_rollout_step_case(gpu, mode, dtype, D, H, L, CB, buckets=BUCKETS):
+    K, A = len(buckets), int(sum(buckets))
+    ps = make_policy_state(gpu, D, H, L, dtype, seed=D + H, critic_bins=CB, buckets=buckets)
     perturb(ps, 1)
     N = 1000
     rng = np.random.default_rng(3)
@@ -132,8 +138,8 @@ def test_lstm_rollout_step(gpu, mode, dtype, D, H, L, CB):
     hd2, cd2 = hd.clone(), cd.clone()
     sh, sc = torch.zeros_like(hd), torch.zeros_like(cd)
     store = torch.zeros((N, D), dtype=dtype, device=gpu)
-    acts = torch.zeros((N, 6), dtype=torch.int32, device=gpu)
-    logp = torch.zeros((N, 6), dtype=torch.float32, device=gpu)
+    acts = torch.full((N, K), -1, dtype=torch.int32, device=gpu)
+    logp = torch.full((N, K), np.nan, dtype=torch.float32, device=gpu)
     vals = torch.zeros(N, dtype=torch.float32, device=gpu)
     ctr = torch.tensor([100, 0, 0, 0], dtype=torch.int64, device=gpu)
     post, keep = _post(gpu, N, done, rng)
@@ -154,12 +160,15 @@ def test_lstm_rollout_step(gpu, mode, dtype, D, H, L, CB):
     np.testing.assert_allclose(vals.cpu().numpy(), V, rtol=tol, atol=vtol)
     np.testing.assert_allclose(hd.float().cpu().numpy(), h2, rtol=tol, atol=tol)
     np.testing.assert_allclose(cd.float().cpu().numpy(), c2, rtol=tol, atol=tol)
-    gum = onat.gumbel_table(5, 6, 107, 3, N, 26)
+    gum = onat.gumbel_table(5, 6, 107, 3, N, A)
     noisy = logits.astype(np.float32) + gum
     got = acts.cpu().numpy()
-    check_actions(noisy, got, BUCKETS, 1e-4 if mode == "f32" else 1e-3, "lstm_rollout_step")
-    elogp, _ = ref.action_stats(logits, BUCKETS, got)
+    check_actions(noisy, got, buckets, 1e-4 if mode == "f32" else 1e-3, "lstm_rollout_step")
+    elogp, _ = ref.action_stats(logits, buckets, got)
     np.testing.assert_allclose(logp.cpu().numpy(), elogp, rtol=tol, atol=tol)
+    for g, nb in enumerate(buckets):
+        if nb == 1:  # a group of one logit: action 0, log-prob exactly 0
+            assert not got[:, g].any() and not logp[:, g].any()
     # bootstrap critic: same values, carry cleared but not advanced
     post2, _ = _post(gpu, N, done, rng)
     v2 = torch.zeros(N, dtype=torch.float32, device=gpu)
@@ -170,15 +179,16 @@ def test_lstm_rollout_step(gpu, mode, dtype, D, H, L, CB):
     assert np.array_equal(cd2.float().cpu().numpy(), cin.astype(np.float32))
 
 
-def _random_store(rng, T, N, D, H, C, ps, mode):
+def _random_store(rng, T, N, D, H, C, ps, mode, buckets=BUCKETS):
+    K = len(buckets)
     obs = ref.rnd(rng.standard_normal((T, N, D)), mode).astype(np.float32)
-    acts = np.stack([rng.integers(0, b, T * N) for b in BUCKETS], -1).astype(np.int32)
-    lp = (rng.standard_normal((T * N, 6)) * 0.3 - 1.6).astype(np.float32)
+    acts = np.stack([rng.integers(0, b, T * N) for b in buckets], -1).astype(np.int32)
+    lp = (rng.standard_normal((T * N, K)) * 0.3 - 1.6).astype(np.float32)
     V = rng.standard_normal((T, N)).astype(np.float32)
     return {
         "obs": obs,
-        "actions": acts.reshape(T, N, 6),
-        "log_probs": lp.reshape(T, N, 6),
+        "actions": acts.reshape(T, N, K),
+        "log_probs": lp.reshape(T, N, K),
         "values": V,
         "advantages": (rng.standard_normal((T, N)) * 2 + 0.3).astype(np.float32),
         "returns": (V + rng.standard_normal((T, N))).astype(np.float32),
@@ -189,11 +199,11 @@ def _random_store(rng, T, N, D, H, C, ps, mode):
     }
 
 
-def _device_store(gpu, st, dtype, C):
+def _device_store(gpu, st, dtype, C, buckets=BUCKETS):
     from madrona_learn.rollouts import RolloutStore
     T, N, D = st["obs"].shape
     H = st["start_h"].shape[2]
-    s = RolloutStore(T, N, D, 6, dtype, gpu, num_chunks=C, rnn_hidden=H)
+    s = RolloutStore(T, N, D, len(buckets), dtype, gpu, num_chunks=C, rnn_hidden=H)
     s.obs.copy_(torch.from_numpy(st["obs"]).to(dtype))
     for k in ("actions", "log_probs", "values", "advantages", "returns", "dones"):
         getattr(s, k).copy_(torch.from_numpy(st[k]))
@@ -206,11 +216,12 @@ HP = {"clip_coef": 0.2, "value_loss_coef": 0.5, "entropy_coef": 0.01,
       "normalize_advantages": True}
 
 
-def _hp(nat):
+def _hp(nat, buckets=BUCKETS, action_groups=None):
+    """action_groups: the oracle's [(n_key, coef), ...] (test_gpu_fullsize.set_group_coefs)."""
+    from tests.test_gpu_fullsize import set_group_coefs
     hp = nat.PPOHparams()
     hp.clip_coef, hp.value_loss_coef = 0.2, 0.5
-    for k in range(6):
-        hp.entropy_coef[k] = 0.01
+    set_group_coefs(hp, len(buckets), 0.01, action_groups)
     hp.normalize_advantages, hp.loss_scale = 1, 1.0
     return hp
 
@@ -218,22 +229,30 @@ def _hp(nat):
 @pytest.mark.parametrize("mode,dtype,D,H,L,CB", CRITIC_CASES)
 @pytest.mark.parametrize("bptt", [32, 16])
 def test_lstm_minibatch_grad(gpu, mode, dtype, D, H, L, CB, bptt):
+    lstm_minibatch_grad_case(gpu, mode, dtype, D, H, L, CB, bptt)
+
+
+def lstm_minibatch_grad_case(gpu, mode, dtype, D, H, L, CB, bptt, buckets=BUCKETS,
+                             action_groups=None):
+    """action_groups: the oracle's [(n_key, coef), ...] (unequal per-key means
+    and entropy coefficients); returns (flat gradient, oracle layout)."""
     from madrona_learn import _native as nat
-    ps = make_policy_state(gpu, D, H, L, dtype, seed=H + 1, critic_bins=CB)
+    hpd = dict(HP, action_groups=action_groups) if action_groups else HP
+    ps = make_policy_state(gpu, D, H, L, dtype, seed=H + 1, critic_bins=CB, buckets=buckets)
     perturb(ps, 9, scale=0.2)
     T, N, mb = 32, 96, 64
     C = T // bptt
     rng = np.random.default_rng(12)
-    st = _random_store(rng, T, N, D, H, C, ps, mode)
+    st = _random_store(rng, T, N, D, H, C, ps, mode, buckets)
     if CB > 1:
         st["returns"] = (st["returns"] * 20.0).astype(np.float32)
-    s = _device_store(gpu, st, dtype, C)
+    s = _device_store(gpu, st, dtype, C, buckets)
     seqs = rng.permutation(C * N)[:mb].astype(np.int32)
     batch = lref.gather_minibatch(st, seqs, bptt)
     adv = batch["advantages"].astype(np.float64)
     P = lref.unflatten(ps.params.cpu().numpy(), oracle_layout(ps))
     ostats = (adv.mean(), adv.var())
-    loss, G, met, _ = lref.ppo_loss_grads(P, batch, HP, BUCKETS, mode, adv_stats=ostats)
+    loss, G, met, _ = lref.ppo_loss_grads(P, batch, hpd, buckets, mode, adv_stats=ostats)
     gflat = lref.flatten(G, oracle_layout(ps))
 
     view = s.view(bptt)
@@ -248,7 +267,7 @@ def test_lstm_minibatch_grad(gpu, mode, dtype, D, H, L, CB, bptt):
     sq = torch.from_numpy(seqs).to(gpu)
     nat.check(L_.mlearn_lstm_ppo_minibatch_grad(
         ps.desc, ps.lstm_desc, view, nat.ptr(s.start_h), nat.ptr(s.start_c), nat.ptr(sq), mb,
-        nat.ptr(stats), _hp(nat), nat.ptr(grad), nat.ptr(out), nat.ptr(ws),
+        nat.ptr(stats), _hp(nat, buckets, action_groups), nat.ptr(grad), nat.ptr(out), nat.ptr(ws),
         nat.stream_handle()), "lstm minibatch grad")
     torch.cuda.synchronize()
     o = out.cpu().numpy()
@@ -276,13 +295,14 @@ def test_lstm_minibatch_grad(gpu, mode, dtype, D, H, L, CB, bptt):
     else:
         # every parameter tensor (the LSTM's included) within the distance bf16
         # rounding itself moves the oracle's gradient; likewise the loss and metrics
-        _, Gf, metf, _ = lref.ppo_loss_grads(P, batch, HP, BUCKETS, "f32", adv_stats=ostats)
+        _, Gf, metf, _ = lref.ppo_loss_grads(P, batch, hpd, buckets, "f32", adv_stats=ostats)
         check_bf16_grad(f"grad_lstm_D{D}_H{H}_L{L}_CB{CB}_bptt{bptt}", g, gflat,
                         lref.flatten(Gf, lay), lay)
-        check_bf16_mean("loss", o[0], loss_rows(met, HP), loss_rows(metf, HP))
+        check_bf16_mean("loss", o[0], loss_rows(met, hpd), loss_rows(metf, hpd))
         check_bf16_mean("Value Loss", o[10], met["Value Loss"], metf["Value Loss"])
         check_bf16_mean("Entropy", o[20], met["Entropy"], metf["Entropy"])
-    assert o[14] == M and o[24] == M * 6
+    assert o[14] == M and o[24] == M * len(buckets)
+    return g, lay
 
 
 def test_lstm_optimizer_step_and_images(gpu):

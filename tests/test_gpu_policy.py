@@ -31,13 +31,14 @@ def make_critic(critic_bins, dtype):
                                                                             num_bins=critic_bins)
 
 
-def make_policy_state(gpu, obs_dim, hidden, layers, dtype, seed=0, critic_bins=1):
+def make_policy_state(gpu, obs_dim, hidden, layers, dtype, seed=0, critic_bins=1,
+                      buckets=BUCKETS):
     import madrona_learn as ml
     from madrona_learn.models import MLP, DenseLayerDiscreteActor
     from madrona_learn.train_state import PolicyState, compile_arch
     ac = ml.ActorCritic(
         backbone=ml.BackboneShared(encoder=ml.BackboneEncoder(net=MLP(hidden, layers, dtype))),
-        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(BUCKETS), dtype),
+        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(list(buckets)), dtype),
         critic=make_critic(critic_bins, dtype))
     arch = compile_arch(ac, obs_dim, dtype)
     return PolicyState(ac, arch, None, gpu, np.random.default_rng(seed))
@@ -86,15 +87,22 @@ CRITIC_CASES = [c + (1,) for c in CASES] + [
 
 @pytest.mark.parametrize("mode,dtype,D,H,L,CB", CRITIC_CASES)
 def test_rollout_step(gpu, mode, dtype, D, H, L, CB):
-    ps = make_policy_state(gpu, D, H, L, dtype, seed=D + H, critic_bins=CB)
+    rollout_step_case(gpu, mode, dtype, D, H, L, CB)
+
+
+def rollout_step_case(gpu, mode, dtype, D, H, L, CB, buckets=BUCKETS):
+    """One rollout step of 1000 envs (the last tile has 8 rows) against the
+    oracle, under the action layout `buckets`."""
+    K, A = len(buckets), int(sum(buckets))
+    ps = make_policy_state(gpu, D, H, L, dtype, seed=D + H, critic_bins=CB, buckets=buckets)
     perturb(ps, 1)
     N = 1000
     rng = np.random.default_rng(2)
     obs = rng.standard_normal((N, D)).astype(np.float32)
     o = torch.from_numpy(obs).to(gpu)
     store = torch.zeros((N, D), dtype=dtype, device=gpu)
-    acts = torch.zeros((N, 6), dtype=torch.int32, device=gpu)
-    logp = torch.zeros((N, 6), dtype=torch.float32, device=gpu)
+    acts = torch.full((N, K), -1, dtype=torch.int32, device=gpu)
+    logp = torch.full((N, K), np.nan, dtype=torch.float32, device=gpu)
     vals = torch.zeros(N, dtype=torch.float32, device=gpu)
     ctr = torch.tensor([100, 0, 0, 0], dtype=torch.int64, device=gpu)
     ps.rollout_step(o, store, acts, logp, vals, (5, 6), ctr[0:1], 7, env_offset=3)
@@ -107,29 +115,33 @@ def test_rollout_step(gpu, mode, dtype, D, H, L, CB):
     np.testing.assert_allclose(vals.cpu().numpy(), V, rtol=tol, atol=vtol)
     if CB > 1:
         assert np.abs(V).max() > 1e-2, "two-hot values should be non-trivial"
-    gum = onat.gumbel_table(5, 6, 107, 3, N, 26)
+    gum = onat.gumbel_table(5, 6, 107, 3, N, A)
     noisy = logits.astype(np.float32) + gum
     got = acts.cpu().numpy()
-    check_actions(noisy, got, BUCKETS, 1e-4 if mode == "f32" else 1e-3, "rollout_step")
-    elogp, _ = ref.action_stats(logits, BUCKETS, got)
+    check_actions(noisy, got, buckets, 1e-4 if mode == "f32" else 1e-3, "rollout_step")
+    elogp, _ = ref.action_stats(logits, buckets, got)
     np.testing.assert_allclose(logp.cpu().numpy(), elogp, rtol=tol, atol=tol)
+    for g, nb in enumerate(buckets):
+        if nb == 1:  # a group of one logit: action 0, log-prob exactly 0
+            assert not got[:, g].any() and not logp[:, g].any()
     # critic only (bootstrap path)
     v2 = torch.zeros(N, dtype=torch.float32, device=gpu)
     ps.critic_only(o, v2)
     assert torch.equal(v2, vals)
 
 
-def _random_store(rng, T, N, D, ps, mode):
+def _random_store(rng, T, N, D, ps, mode, buckets=BUCKETS):
+    K = len(buckets)
     obs = ref.rnd(rng.standard_normal((T, N, D)), mode).astype(np.float32)
     P = ref.unflatten(ps.params.cpu().numpy(), oracle_layout(ps))
     logits, V, _ = ref.forward(P, obs.reshape(T * N, D), mode)
-    acts = np.stack([rng.integers(0, b, T * N) for b in BUCKETS], -1).astype(np.int32)
-    lp, _ = ref.action_stats(logits, BUCKETS, acts)
+    acts = np.stack([rng.integers(0, b, T * N) for b in buckets], -1).astype(np.int32)
+    lp, _ = ref.action_stats(logits, buckets, acts)
     lp = (lp + rng.standard_normal(lp.shape) * 0.1).astype(np.float32)  # old policy != new
     return {
         "obs": obs,
-        "actions": acts.reshape(T, N, 6),
-        "log_probs": lp.reshape(T, N, 6),
+        "actions": acts.reshape(T, N, K),
+        "log_probs": lp.reshape(T, N, K),
         "values": V.astype(np.float32).reshape(T, N),
         "advantages": (rng.standard_normal((T, N)) * 2 + 0.3).astype(np.float32),
         "returns": (V.reshape(T, N) + rng.standard_normal((T, N))).astype(np.float32),
@@ -137,10 +149,10 @@ def _random_store(rng, T, N, D, ps, mode):
     }
 
 
-def _device_store(gpu, st, dtype):
+def _device_store(gpu, st, dtype, buckets=BUCKETS):
     from madrona_learn.rollouts import RolloutStore
     T, N, D = st["obs"].shape
-    s = RolloutStore(T, N, D, 6, dtype, gpu)
+    s = RolloutStore(T, N, D, len(buckets), dtype, gpu)
     s.obs.copy_(torch.from_numpy(st["obs"]).to(dtype))
     s.actions.copy_(torch.from_numpy(st["actions"]))
     s.log_probs.copy_(torch.from_numpy(st["log_probs"]))

@@ -18,11 +18,12 @@ pytestmark = pytest.mark.gpu
 BUCKETS = [4, 8, 5, 5, 2, 2]
 
 
-def make_cfg(dtype, N=64, H=64, T=32, chunks=1, mb=16, epochs=2, seed=5, critic_bins=1):
+def make_cfg(dtype, N=64, H=64, T=32, chunks=1, mb=16, epochs=2, seed=5, critic_bins=1,
+             buckets=BUCKETS):
     import madrona_learn as ml
     return ml.TrainConfig(
         num_worlds=N, num_agents_per_world=1, num_updates=1,
-        actions={"actions": ml.DiscreteActionsConfig(BUCKETS)}, steps_per_update=T,
+        actions={"actions": ml.DiscreteActionsConfig(list(buckets))}, steps_per_update=T,
         lr=3e-4, algo=ml.PPOConfig(num_epochs=epochs, minibatch_size=mb, clip_coef=0.2,
                                    value_loss_coef=0.5, entropy_coef={"actions": 0.01},
                                    max_grad_norm=0.5),
@@ -30,22 +31,24 @@ def make_cfg(dtype, N=64, H=64, T=32, chunks=1, mb=16, epochs=2, seed=5, critic_
         dreamer_v3_critic=critic_bins > 1, compute_dtype=dtype)
 
 
-def make_policy(dtype, H, L=2, critic_bins=1):
+def make_policy(dtype, H, L=2, critic_bins=1, buckets=BUCKETS):
     import madrona_learn as ml
     from madrona_learn.models import MLP, DenseLayerCritic, DenseLayerDiscreteActor, DreamerV3Critic
     critic = DenseLayerCritic(dtype) if critic_bins == 1 else DreamerV3Critic(dtype, num_bins=critic_bins)
     return ml.Policy(actor_critic=ml.ActorCritic(
         backbone=ml.BackboneShared(encoder=ml.BackboneEncoder(net=MLP(H, L, dtype))),
-        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(BUCKETS), dtype),
+        actor=DenseLayerDiscreteActor(ml.DiscreteActionsConfig(list(buckets)), dtype),
         critic=critic), obs_preprocess=ml.ObservationsCaster.create(dtype))
 
 
-def _setup(gpu, dtype, N=64, H=64, D=64, chunks=1, mb=16, use_graph=False, critic_bins=1):
+def _setup(gpu, dtype, N=64, H=64, D=64, chunks=1, mb=16, use_graph=False, critic_bins=1,
+           buckets=BUCKETS):
     import madrona_learn as ml
     from madrona_learn.envs import DummyVecEnv
-    env = DummyVecEnv(N, D, 6, seed=2, device=gpu)
-    cfg = make_cfg(dtype, N=N, H=H, chunks=chunks, mb=mb, critic_bins=critic_bins)
-    mgr = ml.init_training(gpu, cfg, env.sim_fns(), make_policy(dtype, H, critic_bins=critic_bins),
+    env = DummyVecEnv(N, D, len(buckets), seed=2, device=gpu)
+    cfg = make_cfg(dtype, N=N, H=H, chunks=chunks, mb=mb, critic_bins=critic_bins, buckets=buckets)
+    mgr = ml.init_training(gpu, cfg, env.sim_fns(),
+                           make_policy(dtype, H, critic_bins=critic_bins, buckets=buckets),
                            use_graph=use_graph)
     return cfg, env, mgr
 
@@ -60,9 +63,23 @@ def _setup(gpu, dtype, N=64, H=64, D=64, chunks=1, mb=16, use_graph=False, criti
     ("bf16", torch.bfloat16, 1, 1, 1024, 256, 256),
     ("f32", torch.float32, 1, 1, 1024, 256, 256)])
 def test_full_update_matches_oracle(gpu, mode, dtype, chunks, CB, N, H, mb):
-    cfg, env, mgr = _setup(gpu, dtype, N=N, H=H, chunks=chunks, mb=mb, critic_bins=CB)
+    full_update_case(gpu, mode, dtype, chunks, CB, N, H, mb)
+
+
+def test_full_update_matches_oracle_mixed_layout(gpu):
+    """The whole update under DiscreteActionsConfig([9, 1, 12, 2]) (groups above
+    8 logits next to a group of one, tests/action_layouts.py), built through
+    init_training."""
+    from tests.action_layouts import LAYOUTS
+    full_update_case(gpu, "f32", torch.float32, 1, 1, 64, 64, 16, buckets=LAYOUTS["mixed"])
+
+
+def full_update_case(gpu, mode, dtype, chunks, CB, N, H, mb, buckets=BUCKETS):
+    A = int(sum(buckets))
+    cfg, env, mgr = _setup(gpu, dtype, N=N, H=H, chunks=chunks, mb=mb, critic_bins=CB,
+                           buckets=buckets)
     ps, ts = mgr.state.policy_states, mgr.state.train_states
-    lay = ref.param_layout(64, H, 2, 26, CB)
+    lay = ref.param_layout(64, H, 2, A, CB)
     p0 = ps.params.cpu().numpy().astype(np.float64)
     oenv = onat.Env(env.N, env.D, env.k0, env.k1, 0)
     oenv.reset()
@@ -71,7 +88,7 @@ def test_full_update_matches_oracle(gpu, mode, dtype, chunks, CB, N, H, mb):
     s = mgr.rollout_mgr.store
     g_acts = s.actions.cpu().numpy()
     # replay the GPU's trajectory on the oracle env + oracle policy
-    ro, _ = ref.rollout(p0, lay, oenv, cfg.steps_per_update, BUCKETS, mgr.rollout.prng_key, 0,
+    ro, _ = ref.rollout(p0, lay, oenv, cfg.steps_per_update, buckets, mgr.rollout.prng_key, 0,
                         mode=mode, gamma=cfg.gamma, actions_override=g_acts)
     assert np.array_equal(s.obs.float().cpu().numpy(), ro["obs"])
     assert np.array_equal(s.rewards.cpu().numpy(), ro["rewards"])
@@ -85,10 +102,10 @@ def test_full_update_matches_oracle(gpu, mode, dtype, chunks, CB, N, H, mb):
     np.testing.assert_allclose(s.env_returns_trace.cpu().numpy(), ro["env_returns_trace"],
                                rtol=1e-6, atol=1e-6)
     # actions equal the oracle's own samples wherever the margin is clear
-    gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, 0, env.N, 26)
+    gum = np.stack([onat.gumbel_table(*mgr.rollout.prng_key, t, 0, env.N, A)
                     for t in range(cfg.steps_per_update)])
     noisy = ro["logits"] + gum
-    check_actions(noisy, g_acts, BUCKETS, 1e-4 if mode == "f32" else 1e-3, "full_update")
+    check_actions(noisy, g_acts, buckets, 1e-4 if mode == "f32" else 1e-3, "full_update")
     # GAE on the GPU's own store is bit-exact with the oracle's f32 recurrence
     adv, ret = ref.gae_f32(s.rewards.cpu().numpy(), s.values.cpu().numpy(),
                            s.dones.cpu().numpy(), s.bootstrap.cpu().numpy(), cfg.gamma,
@@ -102,7 +119,7 @@ def test_full_update_matches_oracle(gpu, mode, dtype, chunks, CB, N, H, mb):
           "normalize_advantages": True}
     zeros = np.zeros_like(p0)
     p1, _, met = ref.ppo_update(
-        p0, (zeros, zeros.copy(), 0), [store], hp, BUCKETS, lay,
+        p0, (zeros, zeros.copy(), 0), [store], hp, buckets, lay,
         ps.init_norms.cpu().numpy().astype(np.float64), num_epochs=2, minibatch_size=mb,
         bptt=cfg.steps_per_update // chunks, key=ts.update_prng_key, epoch_base=0, mode=mode,
         lr=3e-4, max_grad_norm=0.5)
@@ -124,7 +141,7 @@ def test_full_update_matches_oracle(gpu, mode, dtype, chunks, CB, N, H, mb):
         # per-tensor bound from the oracle's own bf16-vs-f32 effect (tests/bf16_bound.py)
         from tests.bf16_bound import check_bf16_update
         pf, _, _ = ref.ppo_update(
-            p0, (zeros, zeros.copy(), 0), [store], hp, BUCKETS, lay,
+            p0, (zeros, zeros.copy(), 0), [store], hp, buckets, lay,
             ps.init_norms.cpu().numpy().astype(np.float64), num_epochs=2, minibatch_size=mb,
             bptt=cfg.steps_per_update // chunks, key=ts.update_prng_key, epoch_base=0,
             mode="f32", lr=3e-4, max_grad_norm=0.5)
