@@ -16,7 +16,7 @@
 //   * a wave owns whole rows -- two 16-row tiles, v_mfma_f32_16x16x32_bf16 --
 //     so LayerNorm statistics are lane-local sums plus two cross-lane adds,
 //     every product's activation operand comes straight from the previous
-//     accumulators, and no barrier follows the prologue;
+//     accumulators, and the staging barrier is the kernel's only one;
 //   * the forward product reads W1 by row (two ds_read_b64 per fragment), the
 //     backward product reads the same image transposed (ds_read_b64_tr_b16);
 //   * the layer-0 weights (K = obs_dim) stream from L2 per tile.
@@ -209,6 +209,8 @@ template <int DS> struct R16In {
     float lp[2];
 };
 
+constexpr int kR16StageWaves = 4;  // waves 0..3 stage the LDS images (split staging, below)
+
 // NW waves per workgroup (8: two per SIMD; 4 or 2: one per SIMD), NT 16-row
 // tiles per wave (rows16_cfg).
 template <bool METRICS, int NW, int NT, int HC>
@@ -280,40 +282,79 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
     // counted wait leaves the images' loads in flight -- and is itself in
     // flight under the LDS writes and the barrier (the writes wait for the
     // images' loads alone, the gather being younger).  Tile 0 takes its wait.
-    static_assert(NW == kR16Waves, "R16Stage stages with kR16Waves waves");
+    //
+    // Split staging.  vmcnt is per wave: a wave that stages cannot start tile
+    // 0's first product under its own image loads (the W_0 fragments' wait
+    // would cover them), but a wave that does not stage can.  So waves 0..3
+    // stage, 32 + 4 image units per thread, and the workgroup's one barrier
+    // is taken by them right after their LDS writes and by waves 4..7 after
+    // tile 0's first product and statistics (X_0 from the gather, W_0 from
+    // L2: nothing of it reads LDS), in front of the first LDS reader, the
+    // layer-0 LayerNorm apply.  Every wave executes exactly one s_barrier.
+    // (Waves 4..7 as the stagers, and two stagers in two rounds: slower than
+    // all eight staging, profiles/step_stage_split_ab.txt.)
+    static_assert(NW == kR16Waves && kR16StageWaves < NW, "some of the kR16Waves waves stage");
+    constexpr int NSW = kR16StageWaves;
+    const bool stager = wave < NSW;
+#ifdef ML_STAMPS
+    uint64_t r16_t_arr = 0, r16_t_pro = 0, r16_t_iss = 0;
+#endif
+    // the workgroup barrier: the writers' LDS stores completed, then a raw
+    // s_barrier -- no fence, which would drain the loads in flight (the
+    // gather; the W_0 fragments are consumed by then)
+    auto wg_barrier = [&]() {
+#ifdef ML_STAMPS
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        r16_t_arr = __builtin_amdgcn_s_memtime();
+        asm volatile("s_barrier" ::: "memory");
+        r16_t_pro = __builtin_amdgcn_s_memtime();
+#else
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+#endif
+    };
     R16In<DS> in;
     {
         uint32_t tl;
         const int64_t rw = (int64_t)ptile * (16 * NT) + (tid & 15);
-        R16Stage<HC> stg;
+        R16Stage<HC, NSW> stg;
         int tb_off = 0;  // this thread's entries of the group tables
         float tb_ec = 0.f, tb_ow = 0.f;
-#ifdef ML_R16_GATHER_FIRST  // (A/B build: the gather ahead of every staging load)
-        load_in(srow_of(rw, (uint32_t)mb_seq[slot_of(rw, tl)]), tid & 63, in);
-#else
         const uint32_t seq0 = (uint32_t)mb_seq[slot_of(rw, tl)];
-#endif
         __builtin_amdgcn_sched_barrier(0);
         // (everything written to LDS below is loaded ahead of the gather: a
-        // wait for a load issued behind it would wait for the gather too)
-        if (tid <= MLEARN_MAX_GROUPS) {
-            tb_off = P.off[tid];
-            tb_ec = tid < MLEARN_MAX_GROUPS ? hp.ecoef[tid] : 0.f;
-            tb_ow = tid < MLEARN_MAX_GROUPS ? hp.objw[tid] : 0.f;
-        }
-        stg.load_params(P, tid);
-        stg.load_images(P, tid);
-#ifndef ML_R16_GATHER_FIRST
-        __builtin_amdgcn_sched_barrier(0);
-        load_in(srow_of(rw, r16_late(seq0)), tid & 63, in);
-        __builtin_amdgcn_sched_barrier(0);
+        // wait for a load issued behind it would wait for the gather too.  The
+        // gather is written out on both sides of the branch: behind a join the
+        // wait for the mb_seq entry would be a full one, images included)
+        if (stager) {
+            if (tid <= MLEARN_MAX_GROUPS) {
+                tb_off = P.off[tid];
+                tb_ec = tid < MLEARN_MAX_GROUPS ? hp.ecoef[tid] : 0.f;
+                tb_ow = tid < MLEARN_MAX_GROUPS ? hp.objw[tid] : 0.f;
+            }
+            stg.load_params(P, tid);
+            stg.load_images(P, tid);
+            __builtin_amdgcn_sched_barrier(0);
+            load_in(srow_of(rw, r16_late(seq0)), tid & 63, in);
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef ML_STAMPS
+#ifdef ML_STAMPS_LANDING  // (the images landed, the gather's 9 loads still in flight)
+            asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
 #endif
-        stg.put(P, smem, tid);
-        int* tab = (int*)(smem + LY::OffTab);
-        if (tid <= MLEARN_MAX_GROUPS) {
-            tab[tid] = tb_off;
-            ((float*)tab)[MLEARN_MAX_GROUPS + 1 + tid] = tb_ec;
-            ((float*)tab)[2 * (MLEARN_MAX_GROUPS + 1) + tid] = tb_ow;
+            r16_t_iss = __builtin_amdgcn_s_memtime();
+#endif
+            stg.put(P, smem, tid);
+            int* tab = (int*)(smem + LY::OffTab);
+            if (tid <= MLEARN_MAX_GROUPS) {
+                tab[tid] = tb_off;
+                ((float*)tab)[MLEARN_MAX_GROUPS + 1 + tid] = tb_ec;
+                ((float*)tab)[2 * (MLEARN_MAX_GROUPS + 1) + tid] = tb_ow;
+            }
+        } else {
+            load_in(srow_of(rw, r16_late(seq0)), tid & 63, in);
+            __builtin_amdgcn_sched_barrier(0);
+#ifdef ML_STAMPS
+            r16_t_iss = __builtin_amdgcn_s_memtime();
+#endif
         }
     }
     const float as0 = adv_st[0], as1 = adv_st[1];
@@ -322,10 +363,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
     VnVals vn{hp.norm_vals != 0, {0.f, 0.f, 0.f, 0.f}};
     if (hp.norm_vals)
         for (int i = 0; i < 4; ++i) vn.v[i] = adv_st[2 + i];
-    __syncthreads();
-#ifdef ML_STAMPS
-    const uint64_t r16_t_pro = __builtin_amdgcn_s_memtime();
-#endif
+    if (stager) wg_barrier();
     const int* t_off = (const int*)(smem + LY::OffTab);
     const float* t_ec = (const float*)t_off + MLEARN_MAX_GROUPS + 1;
     const float* t_ow = t_ec + MLEARN_MAX_GROUPS + 1;
@@ -351,13 +389,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
 
 #pragma clang loop unroll(disable)
     for (int tt = 0; tt < NT; ++tt) {
-        // the lane index through an opaque copy per tile: otherwise every
-        // lane-derived LDS / weight address of the body is hoisted out of the
-        // tile loop and held live across it (rollout kernel, DESIGN.md §3)
 #ifdef ML_STAMPS
         uint64_t r16_st[13];
 #endif
         R16_STAMP(0);
+        // waves 4..7 hand back the priority they took in tile 0 (below)
+        if (NW > 4 && NT > 1 && tt == NT - 1 && wave >= NW / 2) __builtin_amdgcn_s_setprio(0);
+        // the lane index through an opaque copy per tile: otherwise every
+        // lane-derived LDS / weight address of the body is hoisted out of the
+        // tile loop and held live across it (rollout kernel, DESIGN.md §3)
         const int lane = r16_late(tid & 63), r = lane & 15, g = lane >> 4;
         const int64_t row0 = (int64_t)ptile * (16 * NT) + 16 * tt;
         const int64_t row = row0 + r;
@@ -412,6 +452,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         uint32_t zw0[kR16NB][2], zw[kR16NB][2], aw[kR16NB][2];
         float mean0, rstd0, mean, rstd;
         r16_fwd_layer<DS, kR16Ring0>(lda0(r16_late(lane)), bf0, zw0, mean0, rstd0);
+        // the waves that do not stage meet the stagers here, ahead of the
+        // kernel's first LDS read (r16_ln_apply's scale / bias)
+        if (tt == 0 && !stager) wg_barrier();
         // (the tile's loads are consumed here, ahead of its first stores)
         sr_n = srow_of(row + 16, r16_late(seq_n));
         // (action | return bits, old log-prob | old value) per task
@@ -454,9 +497,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         R16_STAMP(3);
         // the second wave of each SIMD (waves 4..7) loses issue arbitration to
         // the first throughout (tile 0 ends ~24 % later); it takes priority from
-        // its first tile's layer-1 output on, so the two finish closer together
-        // (update 8.43-8.50 -> 8.36-8.38 ms on one box; from the last tile's
-        // start: -1..2 % kernel time; from the kernel's start: slower)
+        // its first tile's layer-1 output to its second tile's start (NT = 2),
+        // so the two finish closer together.  (Held to the kernel's end it
+        // over-corrects: waves 0..3 then end ~17 % after waves 4..7; handed
+        // back later in tile 1, inside tile 0, or never taken: slower,
+        // profiles/step_stage_split_ab.txt.  From the kernel's start: slower.)
         if (NW > 4 && tt == 0 && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
 #ifndef ML_PROBE_NO_A0  // (timing probe only)
         r16_store_rows((bf16*)ws.a[0] + r16_late(row) * kR16H, aw, g);  // A_0 rows
@@ -673,7 +718,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
     r16_put_cols(prev_cp, cb0, cg0, lane);
 
 #ifdef ML_STAMPS
-    {  // entry, after the prologue, end (last stores completed), in tile 0's row
+    {  // entry, the barrier's release, end (last stores completed), in tile 0's
+       // row; at NT = 2, in tile 1's row: this wave's arrival at the barrier
+       // and the point where its prologue loads were all issued
         __builtin_amdgcn_s_waitcnt(0);
         const uint64_t t_end = __builtin_amdgcn_s_memtime();
         if (ws.stamps && (tid & 63) == 0) {
@@ -681,6 +728,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
             st[13] = r16_t_entry;
             st[14] = r16_t_pro;
             st[15] = t_end;
+            if (NT > 1) {
+                st[16 + 13] = r16_t_arr;
+                st[16 + 14] = r16_t_iss;
+            }
         }
     }
 #endif

@@ -258,16 +258,19 @@ __device__ inline void r16_store_rows_keep(bf16* rowp, const uint32_t (&w)[kR16N
 // A LayerNorm pass's per-block scale / bias reads (features 16b + 4g .. +3,
 // f32, LDS) one block ahead: take(following) hands over the values loaded
 // last and issues block `following`'s reads (< 0: none), so each read has a
-// block's arithmetic to land.  Each take is a scheduling fence and each read
-// index opaque: otherwise the compiler issues all 16 blocks' reads up front
-// (128 registers).
+// block's arithmetic to land.  Each take is a scheduling fence (otherwise
+// the compiler issues all 16 blocks' reads up front, 128 registers) and the
+// lane's offset is one opaque value per pass, so a block's 64-byte step and
+// the bias row are ds immediate offsets, no address arithmetic per read.
 struct R16GB {
     const float* gm;
-    int g;
+    int o;
     float4 G, B;
-    __device__ R16GB(const float* gm_, int g_, int first) : gm(gm_), g(g_) { load(first); }
+    __device__ R16GB(const float* gm_, int g, int first) : gm(gm_), o(r16_late(4 * g)) {
+        load(first);
+    }
     __device__ void load(int b) {
-        const int f0 = r16_late(16 * b + 4 * g);
+        const int f0 = 16 * b + o;
         G = *(const float4*)(gm + f0);
         B = *(const float4*)(gm + kR16H + f0);
     }
@@ -329,24 +332,33 @@ __device__ inline uint32_t r16_udiv(uint32_t n, uint32_t mag, int sh) {
 // bias of both layers, head bias.  In two halves, the global loads (images,
 // then parameters) and the LDS writes, so that a caller can issue loads of
 // its own between them: r16_stage runs them back to back.
-template <int HC = kR16HC> struct R16Stage {
+// NSW of the workgroup's waves stage, threads tid < 64 NSW (the rollout
+// kernels: all eight; the minibatch step: four, while the other waves start
+// their first tile).
+template <int HC = kR16HC, int NSW = kR16Waves> struct R16Stage {
     typedef R16Lay<HC> LY;
-    static constexpr int N1 = kR16H * kR16H * 2 / 16 / (64 * kR16Waves);  // 16 per thread
-    u4r v1[N1], vh[2];
-    float pv[2], hbv;
+    static constexpr int NTH = 64 * NSW;                          // staging threads
+    static constexpr int N1 = kR16H * kR16H * 2 / 16 / NTH;       // W1 units per thread
+    static constexpr int NH = 32 * kR16H * 2 / 16 / NTH;          // head image units (HC = 32)
+    static constexpr int NP = 2 * 2 * kR16H / NTH;                // LayerNorm parameters
+    static_assert(N1 * NTH == kR16H * kR16H / 8 && NH * NTH == 32 * kR16H / 8 &&
+                      NP * NTH == 4 * kR16H && HC <= NTH && 64 <= NTH,
+                  "the staging threads divide the images and cover the head bias and bins");
+    u4r v1[N1], vh[NH];
+    float pv[NP], hbv;
     __device__ inline void load_images(const PolicyK& P, int tid) {
         const u4r* src1 = (const u4r*)P.wt[1];
         const u4r* srch = (const u4r*)P.head_t;
 #pragma unroll
-        for (int i = 0; i < N1; ++i) v1[i] = src1[tid + i * 64 * kR16Waves];
+        for (int i = 0; i < N1; ++i) v1[i] = src1[tid + i * NTH];
         if (HC == 32)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) vh[i] = srch[tid + i * 64 * kR16Waves];
+            for (int i = 0; i < NH; ++i) vh[i] = srch[tid + i * NTH];
     }
     __device__ inline void load_params(const PolicyK& P, int tid) {
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            const int j = tid + i * 64 * kR16Waves, l = j >> 9, c = j & 511;
+        for (int i = 0; i < NP; ++i) {
+            const int j = tid + i * NTH, l = j >> 9, c = j & 511;
             pv[i] = c < kR16H ? P.lns[l][c] : P.lnb[l][c - kR16H];
         }
         hbv = tid < HC ? P.head_b[tid] : 0.f;
@@ -365,12 +377,12 @@ template <int HC = kR16HC> struct R16Stage {
             *(u2r*)(img + r16_off(n, 4 * s16 + 2 + h)) = u2r{v[2], v[3]};
         };
 #pragma unroll
-        for (int i = 0; i < N1; ++i) put1(w1img, tid + i * 64 * kR16Waves, v1[i]);
+        for (int i = 0; i < N1; ++i) put1(w1img, tid + i * NTH, v1[i]);
         if (HC == 32)
 #pragma unroll
-            for (int i = 0; i < 2; ++i) put1(whimg, tid + i * 64 * kR16Waves, vh[i]);
+            for (int i = 0; i < NH; ++i) put1(whimg, tid + i * NTH, vh[i]);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) gb[tid + i * 64 * kR16Waves] = pv[i];
+        for (int i = 0; i < NP; ++i) gb[tid + i * NTH] = pv[i];
         if (tid < HC) hb[tid] = hbv;
         if (HC != 32 && tid < P.CB)  // the two-hot critic's bin values (dists.py:128-141)
             ((float*)(smem + LY::OffBins))[tid] = twohot_bin(tid, P.CB);

@@ -54,6 +54,21 @@ l0n = st[1::2, 1] - st[1::2, 0]
 print("tile 0 kernel entry -> end of layer 0 (median / mean / max):", np.median(h0),
       float(h0.mean()), h0.max(), "| of which after the prologue", np.median(w0[:, 1] - w0[:, 14]),
       "| last tile's layer 0", np.median(l0n), float(l0n.mean()), l0n.max())
+# split staging (tile 1's row, slots 13 / 14: the wave's arrival at the
+# workgroup barrier and the point where its prologue loads were all issued --
+# with -DML_STAMPS_LANDING, on the staging waves, where the images had landed;
+# zero in builds from before the split), per wave group, from the wave's entry
+if st[1::2, 13].any():
+    ent = w0[:, 13]
+    cols = {"prologue loads issued": st[1::2, 14] - ent, "arrival at the barrier": st[1::2, 13] - ent,
+            "barrier release": w0[:, 14] - ent, "end of layer 0": h0,
+            "waiting at the barrier": w0[:, 14] - st[1::2, 13]}
+    for gname, sl in (("waves 0-3", slice(0, 4)), ("waves 4-7", slice(4, 8))):
+        print(f"{gname} (cycles from the wave's entry, median / max):",
+              " | ".join(f"{k} {np.median(v.reshape(-1, 8)[:, sl]):.0f} {v.reshape(-1, 8)[:, sl].max()}"
+                         for k, v in cols.items()))
+    print("by wave index (median): arrival", [int(x) for x in np.median(cols["arrival at the barrier"].reshape(-1, 8), 0)],
+          "release", [int(x) for x in np.median(cols["barrier release"].reshape(-1, 8), 0)])
 # per workgroup (8 waves, one CU): wave time entry..end by wave index, and the
 # spread inside a workgroup vs across workgroups
 tw = (w0[:, 15] - w0[:, 13]).reshape(-1, 8)
