@@ -51,14 +51,8 @@ constexpr int kRowAlign = 64;  // Mp granularity of the update (an even number o
 #ifndef ML_WG_SETS
 #define ML_WG_SETS 2  // weight-gradient chunks in flight (register sets of staged rows)
 #endif
-#ifndef ML_WG_GLDS
-#define ML_WG_GLDS 1  // bf16 weight-gradient tiles staged by LDS-DMA (global_load_lds) pipelines
-#endif
 #ifndef ML_WG_STAGES
 #define ML_WG_STAGES 2  // LDS stages of the LDS-DMA pipeline (S - 1 chunks in flight)
-#endif
-#ifndef ML_WG_SLAB_NT
-#define ML_WG_SLAB_NT 1  // LDS-DMA tile: split-K slabs stored nontemporal
 #endif
 #ifndef ML_WG_WAVES
 #define ML_WG_WAVES 3  // waves per SIMD the weight-gradient kernel is register-budgeted for

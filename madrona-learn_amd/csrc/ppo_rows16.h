@@ -475,14 +475,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         }
         R16_STAMP(1);
         // X_0 rows for the weight gradient (16 bytes per lane and k-step)
-#ifndef ML_PROBE_NO_X0  // (timing probe only: numerics invalid without the store)
         {
             bf16* xrow = (bf16*)ws.x0 + r16_late(row) * D;
 #pragma unroll
             for (int s = 0; s < DS; ++s)
                 r16_st16(xrow + 32 * s + 8 * g, __builtin_bit_cast(u4r, xf[s]));
         }
-#endif
         // the previous tile's layer-0 dZ rows go out behind this tile's loads
         if (tt > 0) {
             r16_store_rows((bf16*)ws.dz[0] + r16_late(prev_row) * kR16H, dz0w, g);
@@ -503,9 +501,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         // back later in tile 1, inside tile 0, or never taken: slower,
         // profiles/step_stage_split_ab.txt.  From the kernel's start: slower.)
         if (NW > 4 && tt == 0 && wave >= NW / 2) __builtin_amdgcn_s_setprio(1);
-#ifndef ML_PROBE_NO_A0  // (timing probe only)
         r16_store_rows((bf16*)ws.a[0] + r16_late(row) * kR16H, aw, g);  // A_0 rows
-#endif
         r16_ln_apply(zw, mean, rstd, gb + 2 * kR16H, g, aw);
         R16_STAMP(4);
         // ---- heads (models.py:122-154): logits / value = rnd(rnd(A_1 Wh) + rnd(b))
@@ -675,7 +671,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         // registers only) to cover the gather; the store row through an
         // opaque copy, so the eight addresses are formed here and not held
         // from the end of layer 0.  The last tile issues nothing.
-#ifndef ML_R16_AHEAD_LATE
         if (kAhead && tt + 1 < NT) {
             __builtin_amdgcn_sched_barrier(0);
             load_in(r16_late(sr_n), lane, in);
@@ -683,7 +678,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
         } else {
             in = R16In<DS>{};  // (dead: otherwise tile tt's set stays live to the loop's end)
         }
-#endif
         R16_STAMP(8);
         f32x4 acc[kR16NB];
 #pragma unroll
@@ -695,15 +689,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu((NW + 3
             },
             [&](int s) { return r16_bfrag(dzw, s); });
         R16_STAMP(9);
-#ifdef ML_R16_AHEAD_LATE  // (A/B build: the issue point behind the W1^T product)
-        if (kAhead && tt + 1 < NT) {
-            __builtin_amdgcn_sched_barrier(0);
-            load_in(r16_late(sr_n), lane, in);
-            __builtin_amdgcn_sched_barrier(0);
-        } else {
-            in = R16In<DS>{};  // (dead: otherwise tile tt's set stays live to the loop's end)
-        }
-#endif
         R16_STAMP(10);
         // ---- layer 0 LayerNorm / ReLU backward
         R16_STAMP(11);

@@ -1,6 +1,8 @@
 """Per-dispatch durations of one kernel from a rocprofv3 kernel_trace.csv,
 split by dispatch parity (the ML_PROBE_WG_TWICE variant launches the
 weight-gradient kernel twice back to back: even = first, odd = second).
+The ML_PROBE_WG_TWICE switch is gone from the source: the parent of the commit
+that split csrc/ppo.hip into ppo_step.h / ppo_wgrad.h / ppo_reduce.h is the last tree that builds the variant.
 usage: wg_pairs.py kernel_trace.csv [name_substring]"""
 import csv
 import statistics
