@@ -22,9 +22,9 @@ from typing import Callable, Dict, Optional
 import numpy as np
 import torch
 
-from . import _native as nat
 from .cfg import EvalConfig
 from .policy import Policy
+from .rollouts import lstm_carry, prep_obs, sim_actions, sim_step
 from .train_state import AssignedPolicyStep, PolicyState, compile_arch, param_layout
 
 ELO_INIT = 1500.0  # eval.py:93
@@ -142,26 +142,6 @@ def static_play_assignments(num_eval_policies, custom_policy_ids, num_teams, tea
     return out.tolist()
 
 
-def _prep_obs(ps, prefix, obs, N):
-    from .rollouts import obs_to_matrix
-    x = prefix(obs, train=False)
-    pre = ps.obs_preprocess
-    if getattr(pre, "prep_fns", None) and isinstance(x, dict) and len(x) == 1:
-        k = next(iter(x))
-        x = {k: pre.prep(k, x[k])}
-    return obs_to_matrix(x, N)
-
-
-def _sim_actions(actions, groups):
-    if len(groups) == 1:
-        return actions
-    out, off = {}, 0
-    for name, b in groups:
-        out[name] = actions[:, off:off + len(b)]
-        off += len(b)
-    return out
-
-
 def eval_policies(dev, eval_cfg: EvalConfig, sim_fns: Dict[str, Callable], policy: Policy,
                   init_sim_ctrl, policy_states, step_cb: Callable, elos=None):
     """eval.py:46-267.  ``policy_states``: one PolicyState or a list (from
@@ -237,20 +217,14 @@ def eval_policies(dev, eval_cfg: EvalConfig, sim_fns: Dict[str, Callable], polic
         z = lambda: torch.zeros((N, arch.lstm_hidden), dtype=arch.dtype, device=device)  # noqa: E731
         rnn_states = ([z()], [z()])  # (c_states, h_states), one layer
         prev_done = torch.zeros((N,), dtype=torch.uint8, device=device)
-        carries = []
-        for p in range(P):
-            c = nat.LstmCarry()
-            es = rnn_states[0][0].element_size()
-            c.c = rnn_states[0][0].data_ptr() + p * B * arch.lstm_hidden * es
-            c.h = rnn_states[1][0].data_ptr() + p * B * arch.lstm_hidden * es
-            c.commit = 1
-            c.clear = prev_done.data_ptr() + p * B  # carry cleared where the last step ended
-            carries.append(c)
+        # (the carry is cleared where the last step ended an episode)
+        carries = [lstm_carry(rnn_states[1][0], rnn_states[0][0], p * B, B, clear=prev_done)
+                   for p in range(P)]
 
     for t in range(int(eval_cfg.num_eval_steps)):
         # (a copy: a sim may write its next observations into the same buffer,
         # and step_cb gets the observations the policies saw)
-        obs = _prep_obs(states[0], prefix, cur_obs, N).clone()
+        obs = prep_obs(states[0], prefix, cur_obs, N).clone()
         if competitive:
             stepper.step(assign, obs, actions, log_probs, values, key, counters[0:1], t,
                          env_offset=0, sample=sample)
@@ -260,19 +234,13 @@ def eval_policies(dev, eval_cfg: EvalConfig, sim_fns: Dict[str, Callable], polic
                 ps.rollout_step(obs[c], None, actions[c], log_probs[c], values[c], key,
                                 counters[0:1], t, env_offset=p * B, sample=sample,
                                 carry=carries[p] if carries else None)
-        out = step_fn({
-            "state": sim_state,
-            "actions": _sim_actions(actions, groups),
-            "resets": resets,
-            "sim_ctrl": init_sim_ctrl,
-            "pbt": {"policy_assignments": assign},
-        })
+        out, rewards, dn = sim_step(step_fn, sim_state, sim_actions(actions, groups), resets,
+                                    init_sim_ctrl, assign)
         sim_state, next_obs = out["state"], out["obs"]
-        rewards = out["rewards"].reshape(-1).float()
-        dones = out["dones"].reshape(-1) != 0
+        dones = dn != 0
         env_returns = rewards + gamma * env_returns  # rollouts.py:938-939
         if carries:
-            prev_done.copy_(dones.view(torch.uint8))
+            prev_done.copy_(dn)
         results = (out.get("pbt") or {}).get("episode_results")
         if results is not None and policy.get_episode_scores is not None:
             if competitive:

@@ -44,6 +44,7 @@ modules cannot be captured, the PPO update alone, else nothing
 """
 
 import ctypes
+import inspect
 from dataclasses import dataclass
 
 import numpy as np
@@ -52,6 +53,13 @@ from torch import nn
 
 from . import _native as nat
 from .dists import DiscreteActionDistributions, PhiloxKey, SymExpTwoHotDistribution
+from .dynamic_scale import DynamicScale
+from .models import LayerNorm, _Dense, action_groups
+from .observations import ObservationsPreprocess, _wrap
+from .pbt import MovingEpisodeScore
+from .ppo import _base
+from .rnn import MultiLayerLSTMCell
+from .train_state import _ckpt_safe
 
 
 @dataclass(frozen=True)
@@ -113,8 +121,6 @@ def _projection_groups(ac):
     with bias; rnn.py:30-36) as separate Dense leaves, each projected to its
     own initial norm -- the same per-gate slots as the fused optimizer
     (optim.hip proj_slot)."""
-    from .models import LayerNorm, _Dense
-    from .rnn import MultiLayerLSTMCell
     groups = []
     for name, m in ac.named_modules():
         top = name.split(".", 1)[0]
@@ -248,7 +254,6 @@ class TorchPolicyState:
             self.layout["params"].append((n, off, tuple(p.shape)))
             off += k
         # episode-score fitness (PBT); the population path is fused-only
-        from .pbt import MovingEpisodeScore
         self.episode_score = MovingEpisodeScore(device)
 
     # -- the reference's obs_preprocess hooks (observations.py:13-68) ----------
@@ -283,7 +288,6 @@ class TorchPolicyState:
         pass  # the modules read the arena directly
 
     def state_dict(self):
-        from .train_state import _ckpt_safe
         return {"params": self.params.detach().cpu(),
                 "obs_pre_state": _ckpt_safe(self.obs_pre_state)}
 
@@ -292,7 +296,6 @@ class TorchPolicyState:
         if sd.get("obs_pre_state") is not None:
             st = _to_device(sd["obs_pre_state"], self.device)
             if self._bare_obs:
-                from .observations import _wrap
                 st = _wrap(st)
             self.obs_pre_state = st
 
@@ -378,7 +381,6 @@ def _nonempty(x):
 
 def _has_state(pre):
     """A preprocess with the reference's stateful hooks (observations.py:13-68)."""
-    from .observations import ObservationsPreprocess
     return isinstance(pre, ObservationsPreprocess) and pre.has_state()
 
 
@@ -447,7 +449,6 @@ class TorchTrainState:
         # params and optimizer state (ppo.py:288-291)
         self.scaler = None
         if ps.compute_dtype == torch.float16:
-            from .dynamic_scale import DynamicScale
             self.scaler = DynamicScale(dev)
             d.skip_nonfinite = 1
         self.optim_desc = d
@@ -498,7 +499,6 @@ class TorchRollout:
 
     def collect(self, rollout_state, gamma):
         m = self.mgr
-        ps = m.policy_state
         s = m.store
         L = nat.lib()
         strm = nat.stream_handle()
@@ -507,20 +507,27 @@ class TorchRollout:
         # the sampling kernel adds it to the step itself (no host read, so the
         # rollout can be captured in a HIP graph)
         ctr = rollout_state.counters[0:1]
-        N = m.N
-        rec = ps.recurrent
-        if m.P > 1:
-            # a population (self-play split, pbt.py:130-133): policy p acts for
-            # env columns [p B, (p + 1) B) (init_training excluded recurrent
-            # and stateful-preprocess populations on this path)
-            return self._collect_population(rollout_state, gamma, key, ctr)
+        N, B = m.N, m.B
+        # a population (self-play split, pbt.py:130-133): policy p acts for env
+        # columns [p B, (p + 1) B), its sampling counters those of its env ids
+        # as in the fused population launch.  Observation statistics and the
+        # recurrent carry: one policy only (init_training excluded recurrent
+        # and stateful-preprocess populations on this path)
+        one = m.P == 1
+        rec = one and m.policy_state.recurrent
+        cols = [(p, ps, slice(p * B, (p + 1) * B)) for p, ps in enumerate(m.policies)]
+
+        def part(obs, c):  # a policy's rows of the sim's observations
+            return obs if one else _slice_obs(obs, c.start, c.stop)
+
         start_state, start_obs = rollout_state.sim_state, rollout_state.cur_obs
-        ps.begin_rollout()
+        if one:
+            m.policy_state.begin_rollout()
         if rec:
             # the live carry in sim order (rollouts.py:898-901, 941-942) and
             # the carry entering every BPTT chunk (rnn_start_states,
             # rollouts.py:528-537), one [C][N][...] tensor per state leaf
-            rollout_state.rnn_states = _to_device(rollout_state.rnn_states, ps.device)
+            rollout_state.rnn_states = _to_device(rollout_state.rnn_states, m.policy_state.device)
             bptt, C = m.bptt, m.C
             if getattr(s, "torch_start", None) is None:
                 s.torch_start = _map_leaves(
@@ -528,108 +535,40 @@ class TorchRollout:
                     rollout_state.rnn_states)
             start_rnn = rollout_state.rnn_states
         for t in range(m.T):
-            obs = rollout_state.cur_obs
-            pre = ps.preprocess(obs)
-            ps.observe(t, obs)
-            rnn_in = ps.rnn0
-            if rec:
-                if t % bptt == 0:
+            for p, ps, c in cols:
+                obs = part(rollout_state.cur_obs, c)
+                pre = ps.preprocess(obs)
+                if one:
+                    ps.observe(t, obs)
+                if rec and t % bptt == 0:
                     _zip_leaves(lambda dst, src: dst[t // bptt].copy_(src), s.torch_start,
                                 rollout_state.rnn_states)
-                rnn_in = rollout_state.rnn_states
-            with torch.no_grad():
-                out, rnn_out = ps.actor_critic.rollout(
-                    PhiloxKey(key[0], key[1], t, m.env_offset, ctr=ctr), rnn_in, pre)
-            ps.codec.encode(pre, s.obs[t])
-            s.actions[t].copy_(out["actions"].reshape(N, -1))
-            s.log_probs[t].copy_(out["log_probs"].reshape(N, -1))
-            s.values[t].copy_(_critic_value(out["critic"]))
-            step_input = {
-                "state": rollout_state.sim_state,
-                "actions": m._sim_actions(t),
-                "resets": m._resets,
-                "sim_ctrl": rollout_state.sim_ctrl,
-                "pbt": {"policy_assignments": rollout_state.policy_assignments},
-            }
-            so = rollout_state.step_fn(step_input)
-            rew = so["rewards"].reshape(-1)
-            rew = (rew if rew.dtype == torch.float32 else rew.float()).contiguous()
-            dn = so["dones"].reshape(-1)
-            dn = (dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)) \
-                .contiguous()
-            nat.check(L.mlearn_rollout_post_step(
-                nat.ptr(rew), nat.ptr(dn), N, nat.ptr(s.rewards[t]), nat.ptr(s.dones[t]),
-                nat.ptr(rollout_state.env_returns), nat.ptr(s.env_returns_trace[t]), gamma, strm),
-                "rollout_post_step")
-            rollout_state.sim_state = so["state"]
-            rollout_state.cur_obs = so["obs"]
-            if rec:  # rnn_reset_fn(rnn_states, dones) (rollouts.py:941-942)
-                rollout_state.rnn_states = ps.actor_critic.clear_recurrent_state(
-                    rnn_out, so["dones"].reshape(-1) != 0)
-        with torch.no_grad():
-            rnn_in = rollout_state.rnn_states if rec else ps.rnn0
-            out, _ = ps.actor_critic.critic_only(rnn_in, ps.preprocess(rollout_state.cur_obs))
-        s.bootstrap.copy_(_critic_value(out["critic"]))
-        rollout_state.sim_state = _carry_back(start_state, rollout_state.sim_state)
-        rollout_state.cur_obs = _carry_back(start_obs, rollout_state.cur_obs)
-        if rec:
-            rollout_state.rnn_states = _carry_back(start_rnn, rollout_state.rnn_states)
-
-    def _step_sim(self, rollout_state, t, gamma):
-        m = self.mgr
-        s = m.store
-        N = m.N
-        step_input = {
-            "state": rollout_state.sim_state,
-            "actions": m._sim_actions(t),
-            "resets": m._resets,
-            "sim_ctrl": rollout_state.sim_ctrl,
-            "pbt": {"policy_assignments": rollout_state.policy_assignments},
-        }
-        so = rollout_state.step_fn(step_input)
-        rew = so["rewards"].reshape(-1)
-        rew = (rew if rew.dtype == torch.float32 else rew.float()).contiguous()
-        dn = so["dones"].reshape(-1)
-        dn = (dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)) \
-            .contiguous()
-        nat.check(nat.lib().mlearn_rollout_post_step(
-            nat.ptr(rew), nat.ptr(dn), N, nat.ptr(s.rewards[t]), nat.ptr(s.dones[t]),
-            nat.ptr(rollout_state.env_returns), nat.ptr(s.env_returns_trace[t]), gamma,
-            nat.stream_handle()), "rollout_post_step")
-        rollout_state.sim_state = so["state"]
-        rollout_state.cur_obs = so["obs"]
-
-    def _collect_population(self, rollout_state, gamma, key, ctr):
-        """rollout_loop for P torch-path policies: per step every policy's
-        ActorCritic.rollout on its own env columns (its sampling counters are
-        those of its env ids, as in the fused population launch), the store
-        columns written, then one sim step and post-step for all envs."""
-        m = self.mgr
-        s = m.store
-        B = m.B
-        start_state, start_obs = rollout_state.sim_state, rollout_state.cur_obs
-        for t in range(m.T):
-            obs = rollout_state.cur_obs
-            for p, ps in enumerate(m.policies):
-                c = slice(p * B, (p + 1) * B)
-                pre = ps.preprocess(_slice_obs(obs, p * B, (p + 1) * B))
                 with torch.no_grad():
-                    out, _ = ps.actor_critic.rollout(
-                        PhiloxKey(key[0], key[1], t, m.env_offset + p * B, ctr=ctr), ps.rnn0,
-                        pre)
+                    out, rnn_out = ps.actor_critic.rollout(
+                        PhiloxKey(key[0], key[1], t, m.env_offset + p * B, ctr=ctr),
+                        rollout_state.rnn_states if rec else ps.rnn0, pre)
                 ps.codec.encode(pre, s.obs[t, c])
                 s.actions[t, c].copy_(out["actions"].reshape(B, -1))
                 s.log_probs[t, c].copy_(out["log_probs"].reshape(B, -1))
                 s.values[t, c].copy_(_critic_value(out["critic"]))
-            self._step_sim(rollout_state, t, gamma)
-        obs = rollout_state.cur_obs
-        for p, ps in enumerate(m.policies):
+            _, rew, dn = m._step_sim(rollout_state, m._sim_actions(t))
+            nat.check(L.mlearn_rollout_post_step(
+                nat.ptr(rew), nat.ptr(dn), N, nat.ptr(s.rewards[t]), nat.ptr(s.dones[t]),
+                nat.ptr(rollout_state.env_returns), nat.ptr(s.env_returns_trace[t]), gamma, strm),
+                "rollout_post_step")
+            if rec:  # rnn_reset_fn(rnn_states, dones) (rollouts.py:941-942)
+                rollout_state.rnn_states = m.policy_state.actor_critic.clear_recurrent_state(
+                    rnn_out, dn != 0)
+        for p, ps, c in cols:  # the bootstrap critic (rollouts.py:607-635)
             with torch.no_grad():
                 out, _ = ps.actor_critic.critic_only(
-                    ps.rnn0, ps.preprocess(_slice_obs(obs, p * B, (p + 1) * B)))
-            s.bootstrap[p * B:(p + 1) * B].copy_(_critic_value(out["critic"]))
+                    rollout_state.rnn_states if rec else ps.rnn0,
+                    ps.preprocess(part(rollout_state.cur_obs, c)))
+            s.bootstrap[c].copy_(_critic_value(out["critic"]))
         rollout_state.sim_state = _carry_back(start_state, rollout_state.sim_state)
         rollout_state.cur_obs = _carry_back(start_obs, rollout_state.cur_obs)
+        if rec:
+            rollout_state.rnn_states = _carry_back(start_rnn, rollout_state.rnn_states)
 
 
 class TorchPPO:
@@ -652,7 +591,6 @@ class TorchPPO:
         return self.base.init_hyperparams(cfg)
 
     def prepare(self, cfg, ps, ts, view, dp, policy_idx=0, start_states=None):
-        from .models import action_groups
         b = self.base
         algo = cfg.algo
         if cfg.filter_advantages or cfg.importance_sample_trajectories:
@@ -702,7 +640,6 @@ class TorchPPO:
             raise ValueError(f"TrainConfig.actions {self.groups} does not match the actor's "
                              f"head {ps.arch.buckets}")
         ec = algo.entropy_coef
-        from .ppo import _base
         self.ecoef = [float(_base(ec[n] if isinstance(ec, dict) else ec)) for n, _ in self.groups]
         self.clip = float(algo.clip_coef)
         self.vcoef = float(algo.value_loss_coef)
@@ -869,7 +806,6 @@ class TorchPPO:
 
 
 def _takes_train(m):
-    import inspect
     try:
         return "train" in inspect.signature(m.forward).parameters
     except (TypeError, ValueError):

@@ -20,17 +20,17 @@ their opponents in ``RolloutState.policy_assignments``.  Everything after the
 rollout is the same code on the narrower store.
 """
 
-import math
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, Optional
+from typing import Any, Dict
 
 import torch
 
 from . import _native as nat
-from .algo_common import compute_advantages, compute_returns
+from .algo_common import _gamma_lambda, compute_advantages, compute_returns
 from . import pbt as _pbt
-from .cfg import DiscreteActionsConfig
+from .models import action_groups
 from .pbt import PBTMatchmakeConfig
+from .train_state import MatchedRolloutStep
 
 
 @dataclass(frozen=True)
@@ -222,29 +222,128 @@ class RolloutStore:
     def view(self, bptt_len, col0=0, ncols=None):
         """Rollout view of env columns [col0, col0 + ncols) (one policy of a
         population; the whole store by default)."""
-        ncols = self.N - col0 if ncols is None else ncols
-        assert 0 <= col0 and col0 + ncols <= self.N
-        D = self.obs.shape[2]
-        K = self.actions.shape[2]
-        v = nat.RolloutView()
-        v.obs = self.obs.data_ptr() + col0 * D * self.obs.element_size()
-        v.actions = self.actions.data_ptr() + col0 * K * 4
-        v.log_probs = self.log_probs.data_ptr() + col0 * K * 4
-        v.advantages = self.advantages.data_ptr() + col0 * 4
-        v.returns = None if self.derive_returns else self._returns.data_ptr() + col0 * 4
-        v.values = self.values.data_ptr() + col0 * 4
-        v.dones = self.dones.data_ptr() + col0
-        v.T = self.T
-        v.bptt_len = bptt_len
-        v.N = ncols
-        v.ld = self.N
-        return v
+        return self.cols(col0, self.N - col0 if ncols is None else ncols).view(bptt_len)
+
+    def cols(self, col0, ncols):
+        """Env columns [col0, col0 + ncols) of every leaf (one policy of a
+        population): their addresses and the descriptors built from them."""
+        return StoreCols(self, col0, ncols)
 
 
 # (order of the metric jobs below; 'Advantages' only with compute_advantages,
 # rollouts.py:482-499)
 ROLLOUT_METRICS = ["Rewards", "Values", "Est Returns", "Env Returns", "Bootstrap Values",
                    "Advantages"]
+
+
+class StoreCols:
+    """Env columns [col0, col0 + ncols) of a RolloutStore.  The one place that
+    turns a column index into an address (a wrong row width here would be an
+    out-of-bounds store from a kernel); the descriptors the kernels take are
+    built from ``ptr``.  Plain ``data_ptr()`` integers: runs on CPU tensors."""
+
+    def __init__(self, store, col0, ncols):
+        assert 0 <= col0 and 0 <= ncols and col0 + ncols <= store.N
+        self.store, self.col0, self.ncols = store, col0, ncols
+
+    @staticmethod
+    def _row_ptr(x, row):
+        """Address of row ``row`` of a contiguous [rows, ...] tensor."""
+        return x.data_ptr() + row * x.stride(0) * x.element_size()
+
+    def ptr(self, leaf, t=None):
+        """Address of column col0 of the store leaf named ``leaf`` ([T][N]...;
+        'returns' is the materialised column), or of its row ``t``; of
+        'bootstrap' ([N]); of chunk ``t`` of 'start_h' / 'start_c' ([C][N][R])."""
+        x = getattr(self.store, "_returns" if leaf == "returns" else leaf)
+        if x.dim() == 1:
+            assert t is None
+            return self._row_ptr(x, self.col0)
+        assert x.shape[1] == self.store.N and 0 <= (t or 0) < x.shape[0]
+        return x.data_ptr() + ((t or 0) * x.stride(0) + self.col0 * x.stride(1)) * x.element_size()
+
+    def view(self, bptt_len):
+        s = self.store
+        v = nat.RolloutView()
+        v.obs, v.actions, v.log_probs = self.ptr("obs"), self.ptr("actions"), self.ptr("log_probs")
+        v.advantages, v.values, v.dones = (self.ptr("advantages"), self.ptr("values"),
+                                           self.ptr("dones"))
+        v.returns = None if s.derive_returns else self.ptr("returns")
+        v.T, v.bptt_len, v.N, v.ld = s.T, bptt_len, self.ncols, s.N
+        return v
+
+    def rollout_out(self, bptt_len, env_returns, gamma):
+        """nat.RolloutOut of a whole-rollout launch into these columns
+        (``env_returns``: the rollout state's [N] running returns); the launch
+        switches and the fused-GAE fields are the caller's."""
+        s = self.store
+        o = nat.RolloutOut()
+        for leaf in ("obs", "actions", "log_probs", "values", "rewards", "dones",
+                     "env_returns_trace", "bootstrap"):
+            setattr(o, leaf, self.ptr(leaf))
+        o.env_returns = self._row_ptr(env_returns, self.col0)
+        if s.start_h is not None:
+            o.start_h, o.start_c = self.start_states()
+        o.T, o.bptt_len, o.ld, o.gamma = s.T, bptt_len, s.N, gamma
+        return o
+
+    def fill_post(self, d, t, rew, dn, env_returns, gamma):
+        """nat.PostStep ``d`` of env step t: the sim's [N] f32 rewards and
+        uint8 dones into row t of the store, the running env returns."""
+        d.rewards, d.dones = self._row_ptr(rew, self.col0), self._row_ptr(dn, self.col0)
+        d.store_rewards, d.store_dones = self.ptr("rewards", t), self.ptr("dones", t)
+        d.env_returns = self._row_ptr(env_returns, self.col0)
+        d.env_returns_trace = self.ptr("env_returns_trace", t)
+        d.gamma = gamma
+        return d
+
+    def metric_jobs(self, nmet, population):
+        """The first ``nmet`` ROLLOUT_METRICS as a nat.MetricJob table
+        (``population``: these columns are a strip of a wider store)."""
+        s = self.store
+        jobs = (nat.MetricJob * len(ROLLOUT_METRICS))()
+        leaves = ["rewards", "values", "returns", "env_returns_trace", "bootstrap", "advantages"]
+        for i, leaf in enumerate(leaves[:nmet]):
+            whole = leaf != "bootstrap"  # a [T][N] leaf
+            jobs[i].x = self.ptr(leaf)
+            if leaf == "returns" and s.derive_returns:  # 'Est Returns' = values + advantages
+                jobs[i].x, jobs[i].x2 = self.ptr("values"), self.ptr("advantages")
+            jobs[i].n = s.T * self.ncols if whole else self.ncols
+            jobs[i].cols = self.ncols if whole and population else 0
+            jobs[i].ld = s.N
+            jobs[i].abs_value = 0
+        return jobs
+
+    def start_states(self):
+        """Addresses of these columns of rnn_start_states ([C][ld][H])."""
+        return self.ptr("start_h"), self.ptr("start_c")
+
+    def carry(self, h, c, t, bptt_len):
+        """LstmCarry of env step t on the live [N][H] carry (h, c) (t = T: the
+        bootstrap critic, which clears the carry where the last step ended an
+        episode but does not advance it); a step that opens a BPTT chunk also
+        writes the chunk's start states."""
+        start = None
+        if t < self.store.T and t % bptt_len == 0:
+            start = (self.ptr("start_h", t // bptt_len), self.ptr("start_c", t // bptt_len))
+        return lstm_carry(h, c, self.col0, self.ncols, start=start,
+                          commit=1 if t < self.store.T else 0)
+
+
+def lstm_carry(h, c, col0, ncols, start=None, commit=1, clear=None):
+    """nat.LstmCarry of env columns [col0, col0 + ncols) of the live [N][H]
+    carry.  ``start``: addresses (start_h, start_c) the entering carry is
+    also written to; ``clear``: uint8 [N], the carry is cleared where set."""
+    assert h.shape == c.shape and col0 + ncols <= h.shape[0]
+    d = nat.LstmCarry()
+    off = col0 * h.stride(0) * h.element_size()
+    d.h, d.c = h.data_ptr() + off, c.data_ptr() + off
+    if start is not None:
+        d.start_h, d.start_c = start
+    d.commit = commit
+    if clear is not None:
+        d.clear = clear.data_ptr() + col0 * clear.element_size()
+    return d
 
 
 def obs_to_matrix(obs, N):
@@ -258,6 +357,56 @@ def obs_to_matrix(obs, N):
     if x.dtype != torch.float32:
         x = x.float()
     return x.contiguous()
+
+
+def prep_obs(policy_state, prefix, obs, N):
+    """The [N, obs_dim] f32 matrix the policy kernels read: the backbone
+    prefix, then the ObservationsEMANormalizer prep_fns (observations.py:99-101)."""
+    x = prefix(obs, train=False)
+    pre = policy_state.obs_preprocess
+    if getattr(pre, "prep_fns", None) and isinstance(x, dict) and len(x) == 1:
+        k = next(iter(x))
+        x = {k: pre.prep(k, x[k])}
+    return obs_to_matrix(x, N)
+
+
+def sim_actions(actions, groups):
+    """The sim's 'actions' input: the [N, K] tensor itself, or with several
+    action groups (models.action_groups) a dict keyed like TrainConfig.actions
+    of [N, K_g] views (rollouts.py:985-1002)."""
+    if len(groups) == 1:
+        return actions
+    out, off = {}, 0
+    for name, b in groups:
+        out[name] = actions[:, off:off + len(b)]
+        off += len(b)
+    return out
+
+
+def rewards_dones(out):
+    """A sim output's rewards as contiguous f32 [N] and dones as contiguous
+    uint8 [N] (0 / 1); both alias the sim's tensors where those already have
+    that form (the post-step descriptors of a captured graph hold their
+    addresses)."""
+    rew = out["rewards"].reshape(-1)
+    if rew.dtype != torch.float32:
+        rew = rew.float()
+    dn = out["dones"].reshape(-1)
+    dn = dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)
+    return rew.contiguous(), dn.contiguous()
+
+
+def sim_step(step_fn, sim_state, actions, resets, sim_ctrl, assignments):
+    """One step of the user's sim.  Returns its output dict and
+    rewards_dones of it."""
+    out = step_fn({
+        "state": sim_state,
+        "actions": actions,
+        "resets": resets,
+        "sim_ctrl": sim_ctrl,
+        "pbt": {"policy_assignments": assignments},
+    })
+    return (out, *rewards_dones(out))
 
 
 class RolloutManager:  # rollouts.py:373-826
@@ -357,38 +506,31 @@ class RolloutManager:  # rollouts.py:373-826
                 z = lambda: torch.zeros((self.N, self.R), dtype=arch.dtype,  # noqa: E731
                                         device=self.policy_state.device)
                 init_rollout_state.rnn_states = ([z()], [z()])
-            self._carries = {}
+        self._carries = {}  # (p, t) -> (address of the carry it was built on, LstmCarry)
         self.env_offset = int(env_offset)
         self.use_advantages = train_cfg.compute_advantages
         dev = self.policy_state.device
         self._resets = torch.zeros((self._cfg.num_worlds, 1), dtype=torch.int32, device=dev)
         self._metrics_ws = torch.zeros(int(nat.lib().mlearn_metrics_workspace_bytes(6)),
                                        dtype=torch.uint8, device=dev)
-        s = self.store
-        TN = self.T * self.B
-        self._jobs = []
         self._nmet = len(ROLLOUT_METRICS) - (0 if self.use_advantages else 1)
-        for p in range(self.P):
-            c0 = p * self.B
-            jobs = (nat.MetricJob * 6)()
-            srcs = [(s.rewards, TN, self.B), (s.values, TN, self.B), (s._returns, TN, self.B),
-                    (s.env_returns_trace, TN, self.B), (s.bootstrap, self.B, 0),
-                    (s.advantages, TN, self.B)]
-            for i, (x, n, cols) in enumerate(srcs[:self._nmet]):
-                jobs[i].x = x.data_ptr() + c0 * 4
-                if i == 2 and s.derive_returns:  # 'Est Returns' = values + advantages
-                    jobs[i].x = s.values.data_ptr() + c0 * 4
-                    jobs[i].x2 = s.advantages.data_ptr() + c0 * 4
-                jobs[i].n = n
-                jobs[i].cols = cols if self.P > 1 else 0
-                jobs[i].ld = self.NT
-                jobs[i].abs_value = 0
-            self._jobs.append(jobs)
+        # policy p's store columns, and the descriptors over them: built once
+        # and kept, a captured graph holds their addresses
+        self._cols = [self.store.cols(p * self.B, self.B) for p in range(self.P)]
+        self._jobs = [c.metric_jobs(self._nmet, self.P > 1) for c in self._cols]
+        self._posts = [[nat.PostStep() for _ in range(self.P)] for _ in range(self.T)]
+        # (matchmaking: one post-step per env step over every column)
+        self._all_cols = self.store.cols(0, self.NT)
+        self._mposts = [nat.PostStep() for _ in range(self.T)] if self.matched else None
+        self._post_keep = [None] * self.T  # the sim's (rewards, dones) a post-step points at
+        self._routs, self._env_descs = {}, {}
+        self._pop_sig = self._pop_buf = None
+        self._act_groups = action_groups(train_cfg.actions)
+        self.get_episode_scores = None  # Policy.get_episode_scores, set by init_training
         if self.matched:
             self._init_matched(init_rollout_state, list(past_policies or []))
 
     def _init_matched(self, rollout_state, past):
-        from .train_state import MatchedRolloutStep
         mm = self._cfg.pbt
         ps0 = self.policy_state
         if getattr(ps0, "generic", False) or self.R:
@@ -426,43 +568,21 @@ class RolloutManager:  # rollouts.py:373-826
         mk = rollout_state.matchmake_key
         step_ctr = rollout_state.counters[0:1]
         asg = rollout_state.policy_assignments
-        if not hasattr(self, "_mposts"):
-            self._mposts = [nat.PostStep() for _ in range(self.T)]
-            self._post_keep = [None] * self.T
         post = None
         for t in range(self.T):
             obs = self.prep_obs(rollout_state.cur_obs)
             self._matched.step(asg, obs, s.obs[t], s.actions[t], s.log_probs[t], s.values[t],
                                self._sim_act, key, step_ctr, t, self.env_offset, sample=True,
                                post=post)
-            out = rollout_state.step_fn({
-                "state": rollout_state.sim_state,
-                "actions": self._sim_actions(t, self._sim_act),
-                "resets": self._resets,
-                "sim_ctrl": rollout_state.sim_ctrl,
-                "pbt": {"policy_assignments": asg},
-            })
-            rew = out["rewards"].reshape(-1)
-            if rew.dtype != torch.float32:
-                rew = rew.float()
-            dn = out["dones"].reshape(-1)
-            dn = dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)
-            rew, dn = rew.contiguous(), dn.contiguous()
-            post = self._mposts[t]
-            post.rewards, post.dones = nat.ptr(rew), nat.ptr(dn)
-            post.store_rewards, post.store_dones = nat.ptr(s.rewards[t]), nat.ptr(s.dones[t])
-            post.env_returns = nat.ptr(rollout_state.env_returns)
-            post.env_returns_trace = nat.ptr(s.env_returns_trace[t])
-            post.gamma = gamma
+            out, rew, dn = self._step_sim(rollout_state, self._sim_actions(t, self._sim_act))
+            post = self._all_cols.fill_post(self._mposts[t], t, rew, dn,
+                                            rollout_state.env_returns, gamma)
             self._post_keep[t] = (rew, dn)
-            rollout_state.sim_state = out["state"]
-            rollout_state.cur_obs = out["obs"]
             # ratings from the matches that ended, under the assignments they
             # were played with (pbt.py:273-343), then the opponents of the next ones
             res = (out.get("pbt") or {}).get("episode_results")
             elos = getattr(tsm, "elos", None)
-            if res is not None and elos is not None and \
-                    getattr(self, "get_episode_scores", None) is not None:
+            if res is not None and elos is not None and self.get_episode_scores is not None:
                 elos.copy_(_pbt.pbt_update_elo(self.get_episode_scores, asg, dn, res, elos,
                                                mm.num_teams, mm.team_size))
             nat.check(L.mlearn_matchmake_update(nat.ptr(asg), nat.ptr(dn), self._mm_desc, mk[0],
@@ -475,7 +595,7 @@ class RolloutManager:  # rollouts.py:373-826
         """Rollout view of policy p's env columns.  With compute_advantages=False
         the surrogate objective reads the returns (ppo.py:139-143): the view's
         advantage column is the returns column."""
-        v = self.store.view(self.bptt, p * self.B, self.B)
+        v = self._cols[p].view(self.bptt)
         if not self.use_advantages:
             v.advantages = v.returns
         return v
@@ -483,53 +603,42 @@ class RolloutManager:  # rollouts.py:373-826
     def start_states(self, p=0):
         """Device pointers of policy p's rnn_start_states columns ([C][ld][H],
         ld = the store's N), as the recurrent minibatch kernel reads them."""
-        s = self.store
-        off = p * self.B * self.R * s.start_h.element_size()
-        return s.start_h.data_ptr() + off, s.start_c.data_ptr() + off
+        return self._cols[p].start_states()
 
     def _carry(self, rollout_state, p, t):
-        """LstmCarry of policy p at env step t (t = T: the bootstrap critic,
-        which clears the carry where the last step ended an episode but does
-        not advance it)."""
-        key = (p, t)
-        d = self._carries.get(key)
+        """LstmCarry of policy p at env step t (StoreCols.carry), cached while
+        the rollout state keeps its carry tensors."""
         c_states, h_states = rollout_state.rnn_states
         h, c = h_states[0], c_states[0]
-        if d is None or d.h != h.data_ptr() + p * self.B * self.R * h.element_size():
-            d = nat.LstmCarry()
-            es = h.element_size()
-            d.h = h.data_ptr() + p * self.B * self.R * es
-            d.c = c.data_ptr() + p * self.B * self.R * es
-            if t < self.T and t % self.bptt == 0:
-                sh = self.store.start_h[t // self.bptt, p * self.B:(p + 1) * self.B]
-                sc = self.store.start_c[t // self.bptt, p * self.B:(p + 1) * self.B]
-                d.start_h, d.start_c = sh.data_ptr(), sc.data_ptr()
-            d.commit = 1 if t < self.T else 0
-            self._carries[key] = d
+        at, d = self._carries.get((p, t), (None, None))
+        if at != h.data_ptr():
+            d = self._cols[p].carry(h, c, t, self.bptt)
+            self._carries[(p, t)] = (h.data_ptr(), d)
         return d
 
     def _sim_actions(self, t, a=None):
-        """The sim's 'actions' input of step t: the [N, K] store slice (or
-        ``a``, the sim-order actions under matchmaking), or with several
-        action groups a dict keyed like TrainConfig.actions of [N, K_g] views
-        (rollouts.py:985-1002)."""
-        from .models import action_groups
-        if not hasattr(self, "_act_groups"):
-            self._act_groups = action_groups(self.train_cfg.actions)
-        a = self.store.actions[t] if a is None else a
-        if len(self._act_groups) == 1:
-            return a
-        out, off = {}, 0
-        for name, b in self._act_groups:
-            out[name] = a[:, off:off + len(b)]
-            off += len(b)
-        return out
+        """The sim's 'actions' input of step t: the [N, K] store slice, or
+        ``a``, the sim-order actions under matchmaking (sim_actions)."""
+        return sim_actions(self.store.actions[t] if a is None else a, self._act_groups)
+
+    def _step_sim(self, rollout_state, actions, stepped=None):
+        """sim_step on the rollout state, which takes the sim's new state and
+        observations (``stepped``: the built-in sim that a policy launch has
+        already stepped; only its outputs are taken)."""
+        if stepped is None:
+            out, rew, dn = sim_step(rollout_state.step_fn, rollout_state.sim_state, actions,
+                                    self._resets, rollout_state.sim_ctrl,
+                                    rollout_state.policy_assignments)
+        else:
+            out = stepped.native_outputs()
+            rew, dn = rewards_dones(out)
+        rollout_state.sim_state = out["state"]
+        rollout_state.cur_obs = out["obs"]
+        return out, rew, dn
 
     def _env_desc(self, sim, p):
         """nat.DummyEnv of policy p's env columns (cached per sim)."""
         key = (id(sim), p)
-        if not hasattr(self, "_env_descs"):
-            self._env_descs = {}
         d = self._env_descs.get(key)
         if d is None:
             d = sim.native_step(p * self.B, self.B)
@@ -540,80 +649,77 @@ class RolloutManager:  # rollouts.py:373-826
         return list(names) + ROLLOUT_METRICS[:self._nmet]
 
     def prep_obs(self, obs):
-        x = self.prefix(obs, train=False)
-        pre = self.policy_state.obs_preprocess
-        if hasattr(pre, "prep_fns") and pre.prep_fns and isinstance(x, dict) and len(x) == 1:
-            k = next(iter(x))
-            x = {k: pre.prep(k, x[k])}  # ObservationsEMANormalizer prep_fns (observations.py:99-101)
-        return obs_to_matrix(x, self.N)
+        return prep_obs(self.policy_state, self.prefix, obs, self.N)
 
-    def _post_desc(self, t, p, rew, dn, rollout_state, gamma):
-        """Post-step descriptor of env step t for policy p's columns
-        (rollouts.py:933-973); the tensors it points at are kept alive until
-        the next collect."""
-        s = self.store
-        if not hasattr(self, "_posts"):
-            self._posts = [[nat.PostStep() for _ in range(self.P)] for _ in range(self.T)]
-            self._post_keep = [None] * self.T
-        c = slice(p * self.B, (p + 1) * self.B)
-        d = self._posts[t][p]
-        d.rewards, d.dones = nat.ptr(rew[c]), nat.ptr(dn[c])
-        d.store_rewards, d.store_dones = nat.ptr(s.rewards[t, c]), nat.ptr(s.dones[t, c])
-        d.env_returns = nat.ptr(rollout_state.env_returns[c])
-        d.env_returns_trace = nat.ptr(s.env_returns_trace[t, c])
-        d.gamma = gamma
+    def _post_descs(self, t, rew, dn, rollout_state, gamma):
+        """Every policy's post-step descriptor of env step t (rollouts.py:
+        933-973); the tensors they point at are kept alive until the next
+        collect."""
         self._post_keep[t] = (rew, dn)
-        return d
+        return [c.fill_post(d, t, rew, dn, rollout_state.env_returns, gamma)
+                for c, d in zip(self._cols, self._posts[t])]
 
     def collect(self, train_state_mgr, rollout_state: RolloutState, metrics, user_hooks):
         """rollouts.py:501-577 restated on the fused kernels."""
-        s = self.store
-        L = nat.lib()
-        strm = nat.stream_handle()
         gamma = float(self._cfg.reward_gamma)
         rollout_state, train_state_mgr.user_state = user_hooks.start_rollouts(
             rollout_state, train_state_mgr.user_state)
+        gae_done = False  # whether the rollout launch already wrote the advantages
         if getattr(self.policy_state, "generic", False):
             # a tree outside the fused kernels: torch modules per step (generic.py)
-            from .generic import TorchRollout
+            from .generic import TorchRollout  # cycle
             TorchRollout(self).collect(rollout_state, gamma)
-            return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
-        if self.matched:
+        elif self.matched:
             self._collect_matched(train_state_mgr, rollout_state, gamma)
-            return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
+        else:
+            sim = rollout_state.native_step
+            obs0 = self.prep_obs(rollout_state.cur_obs)
+            if sim is not None and obs0.data_ptr() == sim.obs.data_ptr() and self.whole_rollout:
+                gae_done = self._collect_whole(train_state_mgr, rollout_state, user_hooks, obs0,
+                                               sim, gamma)
+            else:
+                self._collect_steps(rollout_state, gamma)
+        return self._finish(train_state_mgr, rollout_state, metrics, user_hooks, gae_done)
+
+    def _collect_whole(self, train_state_mgr, rollout_state, user_hooks, obs0, sim, gamma):
+        """The built-in sim: every step + the bootstrap in one launch per
+        policy, or one launch for the whole population.  Returns whether the
+        launch computed the advantages too."""
+        key = rollout_state.prng_key
+        step_ctr = rollout_state.counters[0:1]
+        B = self.B
+        fuse = False
+        if not self._population_rollout(rollout_state, obs0, sim, key, step_ctr, gamma):
+            # one policy: GAE rides the rollout launch (mlearn_rollout_out.advantages:
+            # fused into the row-split kernel's epilogue) where nothing may
+            # change the rollout between the two (no finish_rollouts hook, no
+            # value normaliser, advantages only)
+            fuse = self.P == 1 and self._gae_in_rollout(train_state_mgr, user_hooks)
+            for p, ps in enumerate(self.policies):
+                o = self._rollout_out(rollout_state, p, gamma)
+                if fuse:
+                    o.advantages = self._cols[p].ptr("advantages")
+                    o.gae_gamma = float(self.train_cfg.gamma)
+                    o.gae_gamma_lambda = _gamma_lambda(self.train_cfg)
+                else:
+                    o.advantages = None
+                ps.rollout_all(obs0[p * B:(p + 1) * B], o, key,
+                               step_ctr, self.env_offset + p * B, self._env_desc(sim, p),
+                               carry=self._carry(rollout_state, p, 0) if self.R else None)
+        out = sim.native_outputs()
+        rollout_state.sim_state = out["state"]
+        rollout_state.cur_obs = out["obs"]
+        return fuse
+
+    def _collect_steps(self, rollout_state, gamma):
+        """One launch per policy and env step, each with the post-step of the
+        step before, and the sim's step between them; then the bootstrap critic."""
+        s = self.store
         key = rollout_state.prng_key
         step_ctr = rollout_state.counters[0:1]
         B = self.B
         posts = [None] * self.P  # post-step of env step t-1, fused into the policy launches of t
         sim = rollout_state.native_step
-        obs0 = self.prep_obs(rollout_state.cur_obs)
-        if sim is not None and obs0.data_ptr() == sim.obs.data_ptr() and self.whole_rollout:
-            # the built-in sim: every step + the bootstrap in one launch per
-            # policy, or one launch for the whole population
-            if not self._population_rollout(rollout_state, obs0, sim, key, step_ctr, gamma):
-                # one policy: GAE rides the rollout launch (mlearn_rollout_out.advantages:
-                # fused into the row-split kernel's epilogue) where nothing may
-                # change the rollout between the two (no finish_rollouts hook, no
-                # value normaliser, advantages only)
-                fuse = self.P == 1 and self._gae_in_rollout(train_state_mgr, user_hooks)
-                for p, ps in enumerate(self.policies):
-                    c = slice(p * B, (p + 1) * B)
-                    o = self._rollout_out(rollout_state, p, gamma)
-                    if fuse:
-                        from .algo_common import _gamma_lambda
-                        o.advantages = s.advantages.data_ptr()
-                        o.gae_gamma = float(self.train_cfg.gamma)
-                        o.gae_gamma_lambda = _gamma_lambda(self.train_cfg)
-                    else:
-                        o.advantages = None
-                    ps.rollout_all(obs0[c], o, key,
-                                   step_ctr, self.env_offset + p * B, self._env_desc(sim, p),
-                                   carry=self._carry(rollout_state, p, 0) if self.R else None)
-                self._gae_done = fuse
-            out = sim.native_outputs()
-            rollout_state.sim_state = out["state"]
-            rollout_state.cur_obs = out["obs"]
-            return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
         for t in range(self.T):
             obs = self.prep_obs(rollout_state.cur_obs)
             # the built-in sim steps inside the policy launches when they read
@@ -626,43 +732,23 @@ class RolloutManager:  # rollouts.py:373-826
                                 sample=True, post=posts[p],
                                 carry=self._carry(rollout_state, p, t) if self.R else None,
                                 env=self._env_desc(sim, p) if fused else None)
-            if fused:
-                out = sim.native_outputs()
-            else:
-                step_input = {
-                    "state": rollout_state.sim_state,
-                    "actions": self._sim_actions(t),
-                    "resets": self._resets,
-                    "sim_ctrl": rollout_state.sim_ctrl,
-                    "pbt": {"policy_assignments": rollout_state.policy_assignments},
-                }
-                out = rollout_state.step_fn(step_input)
-            rew = out["rewards"].reshape(-1)
-            if rew.dtype != torch.float32:
-                rew = rew.float()
-            dn = out["dones"].reshape(-1)
-            dn = dn.view(torch.uint8) if dn.dtype == torch.bool else (dn != 0).view(torch.uint8)
-            rew, dn = rew.contiguous(), dn.contiguous()
-            posts = [self._post_desc(t, p, rew, dn, rollout_state, gamma)
-                     for p in range(self.P)]
-            rollout_state.sim_state = out["state"]
-            rollout_state.cur_obs = out["obs"]
+            out, rew, dn = self._step_sim(rollout_state, None if fused else self._sim_actions(t),
+                                          stepped=sim if fused else None)
+            posts = self._post_descs(t, rew, dn, rollout_state, gamma)
             # population fitness from the episodes that ended (pbt_update_fitness,
             # pbt.py:382-470; episode_results from the sim's 'pbt' output)
             res = (out.get("pbt") or {}).get("episode_results")
-            if res is not None and getattr(self, "get_episode_scores", None) is not None:
-                from .pbt import pbt_update_fitness
-                pbt_update_fitness([(ps.episode_score, p * B, B)
-                                    for p, ps in enumerate(self.policies)],
-                                   self.get_episode_scores(res), dn,
-                                   team_size=self.train_cfg.num_agents_per_world)
+            if res is not None and self.get_episode_scores is not None:
+                _pbt.pbt_update_fitness([(ps.episode_score, p * B, B)
+                                         for p, ps in enumerate(self.policies)],
+                                        self.get_episode_scores(res), dn,
+                                        team_size=self.train_cfg.num_agents_per_world)
         # bootstrap values (rollouts.py:607-635), with the last post-step
         obs = self.prep_obs(rollout_state.cur_obs)
         for p, ps in enumerate(self.policies):
             c = slice(p * B, (p + 1) * B)
             ps.critic_only(obs[c], s.bootstrap[c], post=posts[p],
                            carry=self._carry(rollout_state, p, self.T) if self.R else None)
-        return self._finish(train_state_mgr, rollout_state, metrics, user_hooks)
 
     def _population_rollout(self, rollout_state, obs0, sim, key, step_ctr, gamma):
         """mlearn_policy_rollout_env_pop over every policy's env columns; False
@@ -686,10 +772,10 @@ class RolloutManager:  # rollouts.py:373-826
         parts = descs + outs + envs + (lstms or []) + (carries or [])
         sig = b"".join(bytes(x) for x in parts) + repr((obs, offs)).encode()
         L = nat.lib()
-        if getattr(self, "_pop_sig", None) != sig:
+        if self._pop_sig != sig:
             if torch.cuda.is_current_stream_capturing():
                 return False  # (the prepare copy cannot run inside a capture)
-            if getattr(self, "_pop_buf", None) is None:
+            if self._pop_buf is None:
                 self._pop_buf = torch.empty(int(L.mlearn_policy_pop_bytes(P)), dtype=torch.uint8,
                                             device=self.policy_state.device)
             arr = lambda T, xs: (T * P)(*xs)  # noqa: E731
@@ -717,41 +803,29 @@ class RolloutManager:  # rollouts.py:373-826
         the GAE objective with returns derived (no value normaliser) and the
         default finish_rollouts hook (which would otherwise see, and may
         rewrite, the rollout before the advantages exist)."""
-        from .train import TrainHooks
         return bool(self.use_advantages and self.store.derive_returns and
                     train_state_mgr.value_norm is None and self.fused_gae and
-                    type(user_hooks).finish_rollouts is TrainHooks.finish_rollouts)
+                    not self._finish_hooked(user_hooks))
+
+    @staticmethod
+    def _finish_hooked(user_hooks):
+        from .train import TrainHooks  # cycle
+        return type(user_hooks).finish_rollouts is not TrainHooks.finish_rollouts
 
     def _rollout_out(self, rollout_state, p, gamma):
         """nat.RolloutOut of policy p's store columns (cached)."""
-        if not hasattr(self, "_routs"):
-            self._routs = {}
-        s = self.store
         key = (p, rollout_state.env_returns.data_ptr())
         o = self._routs.get(key)
         if o is None:
-            c0 = p * self.B
-            o = nat.RolloutOut()
-            o.obs = s.obs.data_ptr() + c0 * s.obs.shape[2] * s.obs.element_size()
-            o.actions = s.actions.data_ptr() + c0 * s.actions.shape[2] * 4
-            o.log_probs = s.log_probs.data_ptr() + c0 * s.log_probs.shape[2] * 4
-            o.values = s.values.data_ptr() + c0 * 4
-            o.rewards = s.rewards.data_ptr() + c0 * 4
-            o.dones = s.dones.data_ptr() + c0
-            o.env_returns_trace = s.env_returns_trace.data_ptr() + c0 * 4
-            o.bootstrap = s.bootstrap.data_ptr() + c0 * 4
-            o.env_returns = rollout_state.env_returns.data_ptr() + c0 * 4
-            if self.R:
-                es = s.start_h.element_size()
-                o.start_h = s.start_h.data_ptr() + c0 * self.R * es
-                o.start_c = s.start_c.data_ptr() + c0 * self.R * es
-            o.T, o.bptt_len, o.ld, o.gamma = self.T, self.bptt, self.N, gamma
+            o = self._cols[p].rollout_out(self.bptt, rollout_state.env_returns, gamma)
             self._routs[key] = o
         o.max_workgroups = int(self.rollout_workgroups)
         o.policy_kernel = int(self.rollout_kernel)
         return o
 
-    def _finish(self, train_state_mgr, rollout_state, metrics, user_hooks):
+    def _finish(self, train_state_mgr, rollout_state, metrics, user_hooks, gae_done=False):
+        """Everything after the rollout itself (``gae_done``: the rollout
+        launch already wrote the advantages)."""
         s = self.store
         L = nat.lib()
         strm = nat.stream_handle()
@@ -760,8 +834,7 @@ class RolloutManager:  # rollouts.py:373-826
         # already normalised observations)
         for ps in self.policies:
             ps.update_obs_norm()
-        from .train import TrainHooks
-        if type(user_hooks).finish_rollouts is not TrainHooks.finish_rollouts:
+        if self._finish_hooked(user_hooks):
             # rollouts.py:726-745: the hook sees the rollout before the
             # advantages exist, plus the critic outputs inverted by the value
             # normaliser; leaves it returns in place of the store's are copied
@@ -778,15 +851,13 @@ class RolloutManager:  # rollouts.py:373-826
             for k, v in (rollouts or {}).items():
                 if k in before and v is not before[k]:
                     before[k].copy_(v.reshape(before[k].shape))
-        if getattr(self, "_gae_done", False):
-            self._gae_done = False  # (the rollout launch wrote the advantages)
-        elif self.use_advantages:
+        if not self.use_advantages:
+            compute_returns(self.train_cfg, s.rewards, s.dones, s.bootstrap, out=s._returns)
+        elif not gae_done:
             compute_advantages(self.train_cfg, s.rewards, s.values, s.dones, s.bootstrap,
                                out_adv=s.advantages,
                                out_ret=False if s.derive_returns else s._returns,
                                value_norm=train_state_mgr.value_norm, norm_cols=self.B)
-        else:
-            compute_returns(self.train_cfg, s.rewards, s.dones, s.bootstrap, out=s._returns)
         for p in range(self.P):
             nat.check(L.mlearn_metrics_f32(self._jobs[p], self._nmet,
                                            nat.ptr(metrics.slots("Rewards", self._nmet, policy=p)),
