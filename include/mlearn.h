@@ -173,7 +173,7 @@ typedef struct mlearn_mlp_policy {
      * to HC = mlearn_head_cols(policy) (32, or 96 when A + critic_bins > 32) */
     const void* head_t;      /* HC*hidden: Bt[n=head col][k=unit] */
     const void* head;        /* HC*hidden: Bt[n=unit][k=head col] */
-    const float* head_bias;  /* [HC] f32 */
+    const float* head_bias;  /* [HC] f32 (critic_kind 1: the bin table follows, see below) */
     /* ObservationsEMANormalizer (observations.py:70-132, EMANormalizer
      * moving_avg.py:48-196).  obs_mu == NULL: the preprocess is a cast. */
     const float* obs_mu;         /* [obs_dim] f32: x' = (x - mu) * inv_sigma, then the cast */
@@ -184,7 +184,20 @@ typedef struct mlearn_mlp_policy {
                                     rollouts.py:670-676) */
     int64_t obs_stats_tiles;     /* >= ceil(N / 32) */
     int32_t obs_stats_steps;
-    int32_t obs_pad;
+    int32_t critic_kind;         /* how critic_bins > 1 logits are read (the field was the
+                                    struct's trailing padding, always 0, until this use):
+                                    0: critic_bins as documented above (scalar / two-hot);
+                                    1: HLGaussCritic (models.py:177-307): critic_bins (odd >= 3)
+                                       categorical logits over the linear bin table that
+                                       follows the head bias: head_bias then points at
+                                       [HC + 2 * critic_bins + 2] floats = the HC biases,
+                                       centers[critic_bins], bounds[critic_bins + 1],
+                                       smoothness.  mlearn_policy_sync_weights writes the
+                                       first HC floats only; the caller fills the tail once.
+                                       (The table gets a pointer of its own the next time
+                                       MLEARN_ABI_VERSION moves.)  The row-split kernels do
+                                       not take this critic: the selectors answer 1.
+                                    anything else: MLEARN_EINVAL */
 } mlearn_mlp_policy;
 
 /* Head width HC of a policy descriptor (-1 if invalid). */
@@ -402,8 +415,9 @@ int32_t mlearn_ppo_step_kernel(const mlearn_mlp_policy* policy, int64_t rows, in
  * 5 x {mean, m2, min, max, count}: 'Loss' {loss,0,loss,loss,1}, 'Action Obj',
  * 'Value Loss', 'Value Errors', 'Entropy' (ppo.py:95-106, 351-362).  With
  * critic_bins > 1 the value loss is the two-hot cross entropy of the returns
- * (ppo.py:169-177, dists.py:171-208); clip/huber value losses need the scalar
- * critic (ppo.py:54-57). */
+ * (ppo.py:169-177, dists.py:171-208), or with policy->critic_kind == 1 the
+ * HL-Gauss loss (ppo.py:178-185, models.py:212-250) over the policy's bin
+ * table; clip/huber value losses need the scalar critic (ppo.py:54-57). */
 int mlearn_ppo_minibatch_grad(const mlearn_mlp_policy* policy, const mlearn_rollout_view* ro,
                               const int32_t* mb_seq, int32_t mb_size, const float* adv_stats,
                               const mlearn_ppo_hparams* hp, float* grad, float* loss_out,

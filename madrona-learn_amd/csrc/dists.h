@@ -175,4 +175,57 @@ __device__ inline float twohot_ce_g(float* lg, int nb, float target, const float
     return loss;
 }
 
+// ---------------------------------------------------------------------------
+// HLGaussDist.loss (models.py:212-250) over the nb critic logits of an
+// HLGaussCritic, by an aligned group of G lanes; mean() is twohot_mean_g over
+// the centres.  centers[nb], bounds[nb + 1] (LDS).  The target, clipped to
+// [centers[0], centers[nb-1]], is smoothed over the bins with a Gaussian of
+// sigma = smooth (bounds[up] - bounds[lo]) around it: cdf_j = erf((bounds_j -
+// t) / (sqrt 2 sigma)), z = cdf_nb - cdf_0, c_j = (1 / z)(cdf_{j+1} - cdf_j),
+// loss = -sum c_j (logit_j - logsumexp).  Lane `sub` evaluates bounds sub,
+// sub + G, ... (one erff per bound); bin j's upper cdf comes from the next
+// lane (the first lane's next bound for the last lane).  cw: nb floats of
+// scratch (LDS) of this row, holding cdf_{j+1} - cdf_j until z is known.
+// Every lane returns the loss and mean(); each lane writes the scaled d loss /
+// d logit (sum c p_j - c_j) of its own bins; the group's reads of other
+// lanes' logits (twohot_mean_g) all precede the writes.
+// ---------------------------------------------------------------------------
+template <int G>
+__device__ inline float hlgauss_ce_g(float* lg, int nb, float target, const float* centers,
+                                     const float* bounds, float smooth, float scale, int sub,
+                                     float* cw, float* mean_out) {
+    const float t = fminf(fmaxf(target, centers[0]), centers[nb - 1]);
+    float cle = 0.f;
+    for (int j = sub; j <= nb; j += G) cle += bounds[j] <= t ? 1.f : 0.f;
+    const int l0 = (int)group_sum<G>(cle) - 1;
+    const int lo = min(max(l0, 0), nb - 1), up = min(max(l0 + 1, 1), nb);
+    const float den = 1.41421354f * (smooth * (bounds[up] - bounds[lo]));
+    auto cdf = [&](int j) { return j <= nb ? erff((bounds[j] - t) / den) : 0.f; };
+    float mx, se;
+    *mean_out = twohot_mean_g<G>(lg, nb, centers, sub, &mx, &se);
+    const float lse = mx + __logf(se);
+    float e = cdf(sub), ends = 0.f, dsum = 0.f;
+    for (int j = sub; j - sub <= nb; j += G) {  // (the same trip count on every lane)
+        const float nx = cdf(j + G);
+        const float hi = __shfl(sub == 0 ? nx : e, (sub + 1) & (G - 1), G);
+        ends += j == nb ? e : 0.f;
+        ends -= j == 0 ? e : 0.f;
+        if (j < nb) {
+            const float d = hi - e;
+            cw[j] = d;
+            dsum += d;
+        }
+        e = nx;
+    }
+    const float rz = 1.0f / group_sum<G>(ends);  // cdf_nb - cdf_0: one lane holds each term
+    const float csum = rz * group_sum<G>(dsum);
+    float ls = 0.f;
+    for (int j = sub; j < nb; j += G) {
+        const float l = lg[j], c = rz * cw[j];
+        ls += c * (l - lse);
+        lg[j] = (csum * (__expf(l - mx) / se) - c) * scale;
+    }
+    return -group_sum<G>(ls);
+}
+
 }  // namespace ml

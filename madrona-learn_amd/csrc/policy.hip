@@ -28,6 +28,7 @@ PolicyK make_policy_k(const mlearn_mlp_policy& p) {
     k.A = p.actions.num_logits;
     k.CB = p.critic_bins;
     k.HC = head_cols(p);
+    k.CK = p.critic_kind;
     for (int i = 0; i <= MLEARN_MAX_GROUPS; ++i) k.off[i] = p.actions.offsets[i];
     for (int l = 0; l < MLEARN_MAX_LAYERS; ++l) {
         k.wt[l] = p.w_t[l];
@@ -59,6 +60,9 @@ int validate_policy(const mlearn_mlp_policy* p) {
     ML_REQUIRE(p->critic_bins == 1 || (p->critic_bins >= 3 && p->critic_bins % 2 == 1),
                "policy: critic_bins must be 1 (scalar critic) or odd >= 3 (two-hot), got %d",
                p->critic_bins);
+    ML_REQUIRE(p->critic_kind == 0 || (p->critic_kind == 1 && p->critic_bins >= 3),
+               "policy: critic_kind must be 0, or 1 (HL-Gauss) with odd critic_bins >= 3 (got "
+               "kind %d, %d bins)", p->critic_kind, p->critic_bins);
     ML_REQUIRE(l.num_logits >= 1 && l.num_logits + p->critic_bins <= MLEARN_HEAD_COLS_MAX,
                "policy: actor logits + critic outputs must be <= %d (got %d + %d)",
                MLEARN_HEAD_COLS_MAX, l.num_logits, p->critic_bins);
@@ -403,7 +407,8 @@ extern "C" int mlearn_policy_pop_prepare(const mlearn_mlp_policy* policies,
         const mlearn_mlp_policy& a = policies[p];
         const mlearn_mlp_policy& b = policies[0];
         ML_REQUIRE(a.dtype == b.dtype && a.hidden == b.hidden && a.num_layers == b.num_layers &&
-                       a.obs_dim == b.obs_dim && head_cols(a) == head_cols(b),
+                       a.obs_dim == b.obs_dim && head_cols(a) == head_cols(b) &&
+                       a.critic_kind == b.critic_kind,
                    "policy_pop_prepare: policy %d's shape differs from policy 0's", p);
         ML_REQUIRE(!lstms == !carries, "policy_pop_prepare: lstms and carries go together");
         const int rc = rollout_env_args(&a, lstms ? &lstms[p] : nullptr,
@@ -634,9 +639,10 @@ extern "C" int mlearn_policy_assigned_prepare(const mlearn_mlp_policy* policies,
         const mlearn_mlp_policy& a = policies[p];
         if (int rc = validate_assigned_policy(&a, who)) return rc;
         ML_REQUIRE(a.dtype == b.dtype && a.obs_dim == b.obs_dim && a.hidden == b.hidden &&
-                       a.num_layers == b.num_layers && a.critic_bins == b.critic_bins,
-                   "%s: policy %d's dtype / obs_dim / hidden / num_layers / critic_bins differ "
-                   "from policy 0's", who, p);
+                       a.num_layers == b.num_layers && a.critic_bins == b.critic_bins &&
+                       a.critic_kind == b.critic_kind,
+                   "%s: policy %d's dtype / obs_dim / hidden / num_layers / critic_bins / "
+                   "critic_kind differ from policy 0's", who, p);
         bool same = a.actions.num_groups == b.actions.num_groups;
         for (int g = 0; same && g <= b.actions.num_groups; ++g)
             same = a.actions.offsets[g] == b.actions.offsets[g];

@@ -95,8 +95,7 @@ __device__ inline void rollout_stage(const PolicyK& P, const LstmK& R) {
     for (int i = tid; i < LY::npar(P.L); i += THREADS) gb[i] = pol_param<H>(P, P.L, i);
     if constexpr (RNN)
         for (int i = tid; i < 4 * H; i += THREADS) rbias[i] = R.bias[i];
-    if (P.CB > 1)
-        for (int i = tid; i < P.CB; i += THREADS) bins[i] = twohot_bin(i, P.CB);
+    stage_critic_bins(P, bins, nullptr, tid, THREADS);
 }
 
 // All T steps + the bootstrap of one 32-env tile (first: the workgroup's

@@ -246,8 +246,7 @@ __device__ __forceinline__ void policy_step_body(
         }
         if constexpr (RNN)
             for (int i = tid; i < 4 * H; i += THREADS) rbias[i] = R.bias[i];
-        if (P.CB > 1)
-            for (int i = tid; i < P.CB; i += THREADS) bins[i] = twohot_bin(i, P.CB);
+        stage_critic_bins(P, bins, nullptr, tid, THREADS);
     }
     const int64_t row0 = (int64_t)tile * 32;
     const int64_t row = tile_env_row<GATHER>(ga, row0, r, N);

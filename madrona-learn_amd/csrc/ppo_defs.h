@@ -402,6 +402,31 @@ __device__ inline void loss_value_twohot_g(const HpK& hp, float* lg, int A, int 
     m.mxerr = fmaxf(m.mxerr, verr);
 }
 
+// HLGaussCritic (ppo.py:178-185): value loss = HLGaussDist.loss of the return
+// against the CB bin logits at lg[A..A+CB); value error = mean() - R.  The
+// group protocol of loss_value_twohot_g; centers[CB] and bounds[CB+1] in
+// LDS, cw = CB floats of LDS scratch of this row.
+template <int G>
+__device__ inline void loss_value_hlgauss_g(const HpK& hp, float* lg, int A, int CB, int HC,
+                                            const float* centers, const float* bounds,
+                                            float smooth, float* cw, float R, int sub,
+                                            LossAcc& m) {
+    float mean;
+    const float vl = hlgauss_ce_g<G>(lg + A, CB, R, centers, bounds, smooth,
+                                     hp.vcoef * hp.inv_s * hp.loss_scale, sub, cw, &mean);
+    for (int j = A + CB + sub; j < HC; j += G) lg[j] = 0.f;
+    if (sub != 0) return;
+    const float verr = fabsf(mean - R);
+    m.svl += vl;
+    m.qvl += vl * vl;
+    m.mnvl = fminf(m.mnvl, vl);
+    m.mxvl = fmaxf(m.mxvl, vl);
+    m.serr += verr;
+    m.qerr += verr * verr;
+    m.mnerr = fminf(m.mnerr, verr);
+    m.mxerr = fmaxf(m.mxerr, verr);
+}
+
 
 // ReLU' threshold: rnd<T>(y) > 0  <=>  y > THR (bf16 round-to-nearest-even
 // sends y <= 2^-134 to zero).

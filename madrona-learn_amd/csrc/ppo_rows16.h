@@ -764,7 +764,8 @@ static R16Cfg rows16_cfg(int64_t Mp) {
 static bool rows16_eligible(const PolicyK& P, int64_t Mp, int HC, int L, int H, bool bf) {
     // head: the scalar critic at width 32, or (round 6) a two-hot critic at
     // width 96 (R16Lay: the head image streamed from L2)
-    const bool head = (HC == 32 && P.CB == 1) || (HC == 96 && P.CB > 1 && P.CB <= 64);
+    // (the HL-Gauss critic, CK = 1, runs on the feature-split step only)
+    const bool head = P.CK == 0 && ((HC == 32 && P.CB == 1) || (HC == 96 && P.CB > 1 && P.CB <= 64));
     return bf && H == kR16H && L == 2 && head && P.D == kR16D && P.K + 1 <= 8 &&
            rows16_cfg(Mp).nw > 0;
 }

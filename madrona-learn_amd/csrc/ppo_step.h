@@ -17,7 +17,8 @@ namespace ml {
 // wave keeps its own Dense outputs in registers for the backward pass.
 // LDS: B fragments [KSH][64], LayerNorm scale/bias [L][2][H], head bias, row
 // statistics [W][32][2], head partials [head_parts][32][HC+1], logits /
-// d logits [32][HC+1], loss partials [W][kLossSlots], critic bins [HC].
+// d logits [32][HC+1], loss partials [W][kLossSlots], critic bins [HC],
+// (HLG) HL-Gauss bin bounds [HC].
 // ---------------------------------------------------------------------------
 // Every spill store of the step kernel is issued AFTER the weight loads of
 // the product that follows it (vmcnt counts loads and stores in issue order,
@@ -36,14 +37,15 @@ template <int H> struct StepCfg {
 
 // Per row tile: B fragments [KSH][64], row statistics [W][32][2], head
 // partials and outputs, loss partials; shared by the RTW row tiles of a
-// workgroup: LayerNorm scale/bias [L][2][H], head bias [HC], critic bins [HC].
+// workgroup: LayerNorm scale/bias [L][2][H], head bias [HC], critic bins [HC],
+// (HLG) HL-Gauss bin bounds [HC].
 template <typename T, int H, int HC> constexpr size_t step_tile_lds() {
     typedef StepCfg<H> C;
     return (size_t)(H / RT<T>::KS) * 64 * sizeof(typename RT<T>::frag) +
            (size_t)(C::W * 64 + (head_parts<HC, C::W>() + 1) * 32 * (HC + 1) + C::W * kLossSlots) * 4;
 }
-template <typename T, int H, int L, int HC, int RTW = 1> static size_t step_lds() {
-    return RTW * step_tile_lds<T, H, HC>() + (size_t)(L * 2 * H + 2 * HC) * 4;
+template <typename T, int H, int L, int HC, int RTW = 1, bool HLG = false> static size_t step_lds() {
+    return RTW * step_tile_lds<T, H, HC>() + (size_t)(L * 2 * H + (HLG ? 3 : 2) * HC) * 4;
 }
 
 // Phases of the step kernel.  kFused: the MLP policy's whole minibatch step.
@@ -101,7 +103,11 @@ __device__ inline void store_rows16(float*, int, f2 (&)[NBW][8], int) {}
 // RTW row tiles of 32 rows per workgroup (kFused): waves w and w + W * rt own
 // the same features of different rows, released by the same barriers, so
 // their weight-fragment loads of every product meet in the CU's L1.
-template <typename T, int H, int L, int MODE = kFused, int HC = MLEARN_HEAD_COLS, int RTW = 1>
+// HLG: the HL-Gauss critic (PolicyK.CK = 1) -- a template parameter, so that
+// the scalar / two-hot instantiations compile to the code they had before it
+// (as a runtime branch it moved their register allocation).
+template <typename T, int H, int L, int MODE = kFused, int HC = MLEARN_HEAD_COLS, int RTW = 1,
+          bool HLG = false>
 __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_waves_per_eu(ML_STEP_WAVES, 8))) void ppo_step_kernel(
     PolicyK P, RolloutK ro, const int32_t* __restrict__ mb_seq, int mb, int64_t M,
     const float* __restrict__ adv_st, HpK hp, WsK ws, RecK rec) {
@@ -129,9 +135,14 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
     float* lred = lg + 32 * LGS;               // [W][kLossSlots]
     float* gb = (float*)(smem + (size_t)RTW * step_tile_lds<T, H, HC>());  // [L][2][H] (shared)
     float* hbias = gb + L * 2 * H;             // [HC]
-    float* bins = hbias + HC;                  // [HC] two-hot critic bins
-    if (kLoss && P.CB > 1)
-        for (int i = tid; i < P.CB; i += THREADS) bins[i] = twohot_bin(i, P.CB);
+    float* bins = hbias + HC;                  // [HC] critic bins (two-hot) / centres (HL-Gauss)
+    float* bounds = bins + HC;                 // (HLG) [HC] HL-Gauss bin bounds (CB + 1 <= HC)
+    if constexpr (HLG) {
+        if (kLoss) stage_critic_bins(P, bins, bounds, tid, THREADS);
+    } else {
+        if (kLoss && P.CB > 1)
+            for (int i = tid; i < P.CB; i += THREADS) bins[i] = twohot_bin(i, P.CB);
+    }
     // LayerNorm / head-bias parameters: loads issued now, written to LDS after
     // the first product (their latency hides under the observation gather)
     constexpr int NPAR = (L * 2 * H + HC + THREADS - 1) / THREADS;
@@ -392,7 +403,11 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
                     continue;
                 }
                 const float R = ret_at(ro, store_row(ro, mb_seq, mb, f));
-                loss_value_twohot_g<G>(hp, lr, P.A, P.CB, HC, bins, R, sub, m);
+                if constexpr (HLG)  // smoothness ends the table; scratch = the row's head partials
+                    loss_value_hlgauss_g<G>(hp, lr, P.A, P.CB, HC, bins, bounds,
+                                            P.head_b[HC + 2 * P.CB + 1], lgp + rr * LGS, R, sub, m);
+                else
+                    loss_value_twohot_g<G>(hp, lr, P.A, P.CB, HC, bins, R, sub, m);
             }
         }
         const float vals[kLossSlots] = {m.sobj, m.qobj, m.mnobj, m.mxobj, m.svl, m.qvl, m.mnvl,
@@ -627,16 +642,19 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
 #ifndef ML_STEP_RTW
 #define ML_STEP_RTW 1  // row tiles per workgroup of the fused MLP step (kFused; 2 measured slower)
 #endif
-template <typename T, int H, int L, int MODE, int HC>
+template <typename T, int H, int L, int MODE, int HC, bool HLG = false>
 static int launch_step_hc(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
                           int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
                           hipStream_t s, const RecK& rec) {
     // ntiles = Mp / 32 is even (Mp is a multiple of 64)
     constexpr int RTW = (MODE == kFused && StepCfg<H>::W * ML_STEP_RTW <= 16) ? ML_STEP_RTW : 1;
-    auto k = ppo_step_kernel<T, H, L, MODE, HC, RTW>;
+    // (only the phases with the loss have an HL-Gauss instantiation)
+    if constexpr (!HLG && (MODE == kFused || MODE == kHeads))
+        if (P.CK) return launch_step_hc<T, H, L, MODE, HC, true>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec);
+    auto k = ppo_step_kernel<T, H, L, MODE, HC, RTW, HLG>;
     // (once per instantiation and device, kept out of graph capture)
     if (int rc = set_lds_attr((const void*)k, 160 * 1024, "ppo_step")) return rc;
-    const size_t lds = step_lds<T, H, L, HC, RTW>();
+    const size_t lds = step_lds<T, H, L, HC, RTW, HLG>();
     const int threads = 64 * StepCfg<H>::W * RTW;
     hipLaunchKernelGGL(k, dim3(ws.ntiles / RTW), dim3(threads), lds, s, P, R, mb_seq, mb, M,
                        adv_st, hp, ws, rec);

@@ -74,7 +74,9 @@ static int rollout16_waves(int64_t N) {
 static bool rollout16_shape(const PolicyK& P, bool bf, bool rnn) {
     // head: the scalar critic at width 32, or (round 6) a two-hot critic at
     // width 96 (R16Lay: the head image streamed from L2)
-    const bool head = (P.HC == 32 && P.CB == 1) || (P.HC == 96 && P.CB > 1 && P.CB <= 64);
+    // (the HL-Gauss critic, CK = 1, runs on the feature-split kernels only)
+    const bool head = P.CK == 0 &&
+                      ((P.HC == 32 && P.CB == 1) || (P.HC == 96 && P.CB > 1 && P.CB <= 64));
     return bf && !rnn && P.H == kR16H && P.L == 2 && head && P.D == kR16D && P.K <= 8 &&
            !P.obs_mu && !P.obs_stats;
 }

@@ -19,6 +19,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "dists.h"
 
 namespace ml {
 
@@ -698,6 +699,8 @@ template <typename T> struct ZIO {
 struct PolicyK {
     int D, H, L, K, A;
     int CB, HC;  // critic outputs (1: scalar, else two-hot bins); head width (32 or 96)
+    int CK;      // mlearn_mlp_policy.critic_kind (1: HL-Gauss, bin table at head_b + HC);
+                 // in the padding ahead of the pointers: the struct's size is unchanged
     const float* obs_mu;   // ObservationsEMANormalizer estimates (null: plain cast)
     const float* obs_inv;
     float* obs_stats;      // per-step per-tile {mean, M2} of the raw observations
@@ -714,6 +717,23 @@ struct PolicyK {
 };
 
 PolicyK make_policy_k(const mlearn_mlp_policy& p);
+
+// The CB bin values of a distributional critic into LDS (bins[CB]): the
+// two-hot critic's symexp bins, or (CK = 1, HL-Gauss) the centres of the
+// policy's table behind the head bias; with `bounds` also that table's CB + 1
+// bin bounds (the update's loss reads them, the rollout's mean() does not).
+__device__ inline void stage_critic_bins(const PolicyK& P, float* bins, float* bounds, int tid,
+                                         int threads) {
+    if (P.CB <= 1) return;
+    if (P.CK == 0) {
+        for (int i = tid; i < P.CB; i += threads) bins[i] = twohot_bin(i, P.CB);
+        return;
+    }
+    const float* tab = P.head_b + P.HC;
+    for (int i = tid; i < P.CB; i += threads) bins[i] = tab[i];
+    if (bounds)
+        for (int i = tid; i <= P.CB; i += threads) bounds[i] = tab[P.CB + i];
+}
 
 // LSTM weights of a recurrent policy (mlearn_lstm); bias is the f32 master.
 struct LstmK {

@@ -25,6 +25,7 @@ MAX_LAYERS = 4
 MAX_GROUPS = 16
 HEAD_COLS = 32       # head width with a scalar critic
 HEAD_COLS_MAX = 96   # head width when actor logits + critic bins exceed 32
+CRITIC_HLGAUSS = 1   # mlearn_mlp_policy.critic_kind of an HLGaussCritic
 
 
 class ActionLayout(Structure):
@@ -40,7 +41,7 @@ class MlpPolicy(Structure):
                 ("head_t", c_void_p), ("head", c_void_p), ("head_bias", c_void_p),
                 ("obs_mu", c_void_p), ("obs_inv_sigma", c_void_p), ("obs_stats", c_void_p),
                 ("obs_stats_tiles", c_int64), ("obs_stats_steps", c_int32),
-                ("obs_pad", c_int32)]
+                ("critic_kind", c_int32)]  # 0: scalar / two-hot; 1: HL-Gauss (CRITIC_HLGAUSS)
 
 
 class MetricJob(Structure):

@@ -9,7 +9,8 @@ modules, as torch ``nn.Module`` s:
 * Fast path: when the tree is one the fused kernels implement
   (``BackboneShared(encoder=BackboneEncoder(net=MLP))`` or
   ``RecurrentBackboneEncoder(net=MLP, rnn=LSTM)``, ``DenseLayerDiscreteActor``,
-  ``DenseLayerCritic`` / ``DreamerV3Critic``) the methods run the HIP
+  ``DenseLayerCritic`` / ``DreamerV3Critic`` / ``HLGaussCritic``; the critic
+  output is then its value, ``mean()`` of a distributional one) the methods run the HIP
   kernels of ``libmlearn.so`` on the parameters of the ``PolicyState`` the
   tree is bound to (``init_training`` binds the training policy; an unbound
   tree compiles one on first use with the reference initialisers).

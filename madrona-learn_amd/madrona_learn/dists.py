@@ -6,6 +6,8 @@ the GPU) and dispatches to the HIP kernels.  RNG: the reference's
 DESIGN.md "RNG".
 """
 
+import math
+
 import torch
 
 from . import _native as nat
@@ -144,3 +146,42 @@ class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
 
     def reshape(self, *shape):
         return SymExpTwoHotDistribution(self.logits.reshape(*shape, self.logits.shape[-1]))
+
+
+class HLGaussDist:  # models.py:177-250 (critic of HLGaussCritic)
+    """Categorical critic over linear bins, trained against a Gaussian-smoothed
+    target.  The torch path's implementation; the fused kernels compute the
+    same mean() / loss in csrc/dists.h (hlgauss_ce_g)."""
+
+    def __init__(self, logits, centers, bounds, smoothness):
+        self.logits = logits.float()
+        self.centers = torch.as_tensor(centers, dtype=torch.float32).to(self.logits.device)
+        self.bounds = torch.as_tensor(bounds, dtype=torch.float32).to(self.logits.device)
+        self.smoothness = float(smoothness)
+
+    def mean(self):
+        c = self.centers
+        mid = (c.shape[-1] - 1) // 2
+        p = torch.softmax(self.logits, -1)
+        lo = (p[..., :mid] * c[:mid]).flip(-1)
+        hi = p[..., mid + 1:] * c[mid + 1:]
+        return (p[..., mid:mid + 1] * c[mid:mid + 1]).sum(-1, keepdim=True) + \
+            (lo + hi).sum(-1, keepdim=True)
+
+    def loss(self, targets):
+        b = self.bounds
+        nbd = b.shape[-1]
+        t = torch.minimum(torch.maximum(targets.float(), self.centers[0]), self.centers[-1])
+        lo0 = (b <= t).int().sum(-1) - 1
+        lo = lo0.clamp(0, nbd - 2)
+        up = (lo0 + 1).clamp(1, nbd - 1)
+        sigma = self.smoothness * (b[up] - b[lo])[..., None]
+        cdf = torch.erf((b - t) / (math.sqrt(2.0) * sigma))
+        z = (cdf[..., -1] - cdf[..., 0])[..., None]
+        c = 1 / z * (cdf[..., 1:] - cdf[..., :-1])
+        logp = self.logits - torch.logsumexp(self.logits, -1, keepdim=True)
+        return -(c * logp).sum(-1, keepdim=True)
+
+    def reshape(self, *shape):
+        return HLGaussDist(self.logits.reshape(*shape, self.logits.shape[-1]), self.centers,
+                           self.bounds, self.smoothness)

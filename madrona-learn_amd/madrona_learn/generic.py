@@ -52,7 +52,8 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .dists import DiscreteActionDistributions, PhiloxKey, SymExpTwoHotDistribution
+from .dists import (DiscreteActionDistributions, HLGaussDist, PhiloxKey,
+                    SymExpTwoHotDistribution)
 from .dynamic_scale import DynamicScale
 from .models import LayerNorm, _Dense, action_groups
 from .observations import ObservationsPreprocess, _wrap
@@ -232,8 +233,11 @@ class TorchPolicyState:
             self.rnn0 = rnn
             out, _ = self.actor_critic.rollout(PhiloxKey(0, 0), rnn, one)
         crit = out["critic"]
-        self.critic_bins = 1 if not isinstance(crit, SymExpTwoHotDistribution) \
+        self.critic_bins = 1 if not isinstance(crit, (SymExpTwoHotDistribution, HLGaussDist)) \
             else int(crit.logits.shape[-1])
+        # what the critic returns (train._check_critic_flags)
+        self.critic_form = "hlgauss" if isinstance(crit, HLGaussDist) else \
+            ("two-hot" if self.critic_bins > 1 else "scalar")
         self.codec = ObsCodec(pre)
         self.arch = GenericArch(obs_dim=self.codec.width, buckets=tuple(int(b) for b in buckets),
                                 dtype=compute_dtype, critic_bins=self.critic_bins)
@@ -481,8 +485,8 @@ class TorchTrainState:
 
 def _critic_value(crit):
     """_compute_value_estimate (rollouts.py:601-605): the scalar critic, or
-    SymExpTwoHotDistribution.mean()."""
-    if isinstance(crit, SymExpTwoHotDistribution):
+    SymExpTwoHotDistribution.mean() / HLGaussDist.mean()."""
+    if isinstance(crit, (SymExpTwoHotDistribution, HLGaussDist)):
         return crit.mean().reshape(-1)
     return crit.float().reshape(-1)
 
@@ -626,8 +630,8 @@ class TorchPPO:
             # ppo.py:57 asserts not normalize_values for distributional
             # critics: the two-hot loss ignores the normaliser, yet GAE would
             # invert the two-hot mean with drifting estimates
-            raise ValueError("normalize_values with a SymExpTwoHotDistribution critic "
-                             "(the reference asserts against it, ppo.py:57)")
+            raise ValueError("normalize_values with a SymExpTwoHotDistribution / HLGaussDist "
+                             "critic (the reference asserts against it, ppo.py:57)")
         if b.vnorm:
             b.vn_est = ts.value_norm_est
             b.vn_count = ts.value_norm_count
@@ -717,6 +721,9 @@ class TorchPPO:
         verr = None
         if isinstance(crit, SymExpTwoHotDistribution):
             vl = crit.two_hot_cross_entropy_loss(R.reshape(-1, 1)).reshape(T, M)
+            V = crit.mean().reshape(T, M)
+        elif isinstance(crit, HLGaussDist):  # ppo.py:178-185
+            vl = crit.loss(R.reshape(-1, 1)).reshape(T, M)
             V = crit.mean().reshape(T, M)
         else:
             V = crit.float().reshape(T, M)

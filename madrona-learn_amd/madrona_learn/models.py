@@ -3,8 +3,8 @@
 Each class is both an architecture description and a torch module:
 
 * fast path: the MI355X engine compiles a recognised ActorCritic tree
-  (BackboneShared/BackboneEncoder + MLP (+ LSTM) + discrete actor + scalar
-  or two-hot critic) into the fused HIP kernels of ``libmlearn.so`` (see
+  (BackboneShared/BackboneEncoder + MLP (+ LSTM) + discrete actor + scalar,
+  two-hot or HL-Gauss critic) into the fused HIP kernels of ``libmlearn.so`` (see
   train_state.compile_arch); its parameters then live in the engine's flat
   arena, created with the reference's initialisers (orthogonal with the
   same scales, zero biases, LayerNorm scale 1 / bias 0);
@@ -166,3 +166,44 @@ class DreamerV3Critic(nn.Module):  # models.py:157-174 (SymExpTwoHotDistribution
     def forward(self, features, train=False):
         from .dists import SymExpTwoHotDistribution
         return SymExpTwoHotDistribution(self.impl(features))
+
+
+class HLGaussCritic(nn.Module):  # models.py:253-307 (HLGaussDist head)
+    """centers [num_bins] (odd, antisymmetric for mean() to be 0 at zero
+    logits) and bounds [num_bins + 1]: f32 arrays, module configuration (not
+    trained, not checkpointed)."""
+
+    def __init__(self, dtype, centers, bounds, smoothness=0.75, weight_init=constant(0.0)):
+        super().__init__()
+        self.dtype = canonical_dtype(dtype)
+        self.centers = np.ascontiguousarray(np.asarray(centers, dtype=np.float32))
+        self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.float32))
+        if self.centers.ndim != 1 or self.bounds.shape != (self.centers.size + 1,):
+            raise ValueError(f"HLGaussCritic: bounds must hold one more value than centers, got "
+                             f"{self.centers.shape} centers and {self.bounds.shape} bounds")
+        self.smoothness = float(smoothness)
+        self.weight_init = weight_init
+        self.num_bins = int(self.centers.size)
+        self._tables = None
+        self.impl = _Dense(self.num_bins, True, self.dtype, weight_init)
+
+    @staticmethod
+    def create(dtype, num_bins=127, min_bound=-100, max_bound=100, smoothness=0.75):
+        # gen_bins (models.py:271-281), float64 then cast: 2 (num_bins // 2) + 1
+        # centres mirrored around 0 (max_bound is not read there either)
+        half = np.linspace(min_bound, 0, num_bins // 2 + 1)
+        bins = np.concatenate([half, -half[:-1][::-1]], axis=0)
+        width = bins[1] - bins[0]
+        bounds = bins - 0.5 * width
+        bounds = np.concatenate([bounds, np.asarray([bounds[-1] + width])], axis=0)
+        return HLGaussCritic(dtype, bins.astype(np.float32), bounds.astype(np.float32),
+                             smoothness=smoothness)
+
+    def forward(self, features, train=False):
+        from .dists import HLGaussDist
+        # the tables on the features' device, copied once (no host copy inside
+        # a captured update)
+        if self._tables is None or self._tables[0].device != features.device:
+            self._tables = tuple(torch.from_numpy(a).to(features.device)
+                                 for a in (self.centers, self.bounds))
+        return HLGaussDist(self.impl(features), *self._tables, self.smoothness)

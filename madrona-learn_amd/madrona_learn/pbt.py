@@ -679,7 +679,8 @@ class PastPolicy:
             from .train_state import PolicyImages
             self.arch = like.arch
             self.device = like.device
-            self.images = PolicyImages(like.arch, like.layout, self.params, self.obs_est)
+            self.images = PolicyImages(like.arch, like.layout, self.params, self.obs_est,
+                                       getattr(getattr(like, "actor_critic", None), "critic", None))
             self.desc = self.images.desc
             self.sync_weights()
 

@@ -352,10 +352,6 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
     if device.type != "cuda":
         raise ValueError(f"device must be a GPU, got {device}")
     torch.cuda.set_device(device)
-    if cfg.hlgauss_critic:
-        raise NotImplementedError(
-            "hlgauss_critic (HLGaussDist, models.py:177-315) is outside the fused path; the "
-            "scalar DenseLayerCritic and the DreamerV3Critic two-hot critic are supported")
     num_policies = 1
     # cross-play / past-play matchmaking (pbt.py:21-255): any portion off pure self play
     matched = False
@@ -421,13 +417,9 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
     from .rollouts import obs_to_matrix
     obs0 = obs_to_matrix(prefix(rollout_state.cur_obs, train=False), sim_batch)
     arch = compile_arch(policy.actor_critic, obs0.shape[1], cfg.compute_dtype)
-    # the loss follows cfg.dreamer_v3_critic (ppo.py:169-218) and the stored
-    # values the critic module (rollouts.py:383-384, 601-605): they must agree
-    if bool(cfg.dreamer_v3_critic) != (arch.critic_bins > 1):
-        raise ValueError(
-            f"TrainConfig.dreamer_v3_critic={cfg.dreamer_v3_critic} but the policy's critic is "
-            f"{type(policy.actor_critic.critic).__name__}: use DreamerV3Critic with "
-            "dreamer_v3_critic=True (the reference default) or DenseLayerCritic with False")
+    _check_critic_flags(cfg, policy.actor_critic.critic,
+                        "hlgauss" if arch.critic_kind else
+                        ("two-hot" if arch.critic_bins > 1 else "scalar"))
     preprocess = policy.obs_preprocess
     obs_key = None
     if preprocess is not None:
@@ -530,6 +522,30 @@ def _matchmaking_problem(cfg, policy, rnn_states, W):
     return None
 
 
+def _check_critic_flags(cfg, critic, form):
+    """The loss follows cfg.dreamer_v3_critic, then cfg.hlgauss_critic
+    (ppo.py:169-218, in that order), and the stored values the critic module's
+    output (rollouts.py:383-384, 601-605): they must agree.  form: what the
+    critic returns, "scalar" / "two-hot" / "hlgauss"."""
+    name = type(critic).__name__
+    dv3, hlg = bool(cfg.dreamer_v3_critic), bool(cfg.hlgauss_critic)
+    want = {"scalar": (False, False), "two-hot": (True, False), "hlgauss": (False, True)}[form]
+    if (dv3, hlg) == want:
+        return
+    if hlg and form != "hlgauss":
+        from .models import DenseLayerCritic, DreamerV3Critic
+        if not isinstance(critic, (DenseLayerCritic, DreamerV3Critic)):
+            raise NotImplementedError(
+                f"hlgauss_critic=True with a {name} critic: HLGaussCritic (models.py:253-307) is "
+                "the HL-Gauss critic implemented here (HLGaussTwoPartCritic is not)")
+    raise ValueError(
+        f"TrainConfig.dreamer_v3_critic={dv3}, hlgauss_critic={hlg} but the policy's critic is "
+        f"{name} ({form}): set dreamer_v3_critic={want[0]} and hlgauss_critic={want[1]} (an "
+        "HLGaussCritic needs dreamer_v3_critic=False: the reference tests dreamer_v3_critic, "
+        "True by default, first), or use DreamerV3Critic / DenseLayerCritic / HLGaussCritic to "
+        "match the flags")
+
+
 def _fused_tree_problem(policy, rollout_state, sim_batch, cfg):
     """None when the fused kernels implement the policy (tree and
     preprocess), else why not (the torch path then trains it).  Only the
@@ -606,9 +622,7 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
         obs_p = rollout_state.cur_obs if P == 1 else _obs_cols(rollout_state.cur_obs, P, i)
         ps = TorchPolicyState(ac, policy.obs_preprocess, device, obs_p, cfg.compute_dtype,
                               buckets, seed)
-        if bool(cfg.dreamer_v3_critic) != (ps.critic_bins > 1):
-            raise ValueError(f"TrainConfig.dreamer_v3_critic={cfg.dreamer_v3_critic} does not "
-                             f"match the policy's critic ({ps.critic_bins} output bins)")
+        _check_critic_flags(cfg, getattr(ac, "critic", None), ps.critic_form)
         dp.broadcast_(ps.params)
         algo = TorchPPO(cfg.algo.setup())
         ts = TorchTrainState(cfg, algo.init_hyperparams(cfg), ps,

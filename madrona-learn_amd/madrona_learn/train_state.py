@@ -21,7 +21,8 @@ from . import _native as nat
 from .actor_critic import (ActorCritic, BackboneEncoder, BackboneShared,
                            RecurrentBackboneEncoder)
 from .cfg import DiscreteActionsConfig, TrainConfig
-from .models import MLP, DenseLayerCritic, DenseLayerDiscreteActor, DreamerV3Critic
+from .models import (MLP, DenseLayerCritic, DenseLayerDiscreteActor, DreamerV3Critic,
+                     HLGaussCritic)
 from .observations import ObservationsEMANormalizer, ObservationsPreprocessNoop
 from .rnn import LSTM
 
@@ -35,6 +36,7 @@ class MlpArch:
     dtype: torch.dtype
     lstm_hidden: int = 0  # width of the LSTM after the trunk (0: feed-forward policy)
     critic_bins: int = 1  # 1: DenseLayerCritic; odd > 1: DreamerV3Critic two-hot bins
+    critic_kind: int = 0  # how critic_bins > 1 logits are read: 0 two-hot, 1 HLGaussCritic
 
     @property
     def num_logits(self):
@@ -122,6 +124,7 @@ def compile_arch(actor_critic: ActorCritic, obs_dim: int, compute_dtype) -> MlpA
         raise NotImplementedError(f"fused path: observation width a multiple of 16 in "
                                   f"[16, 256], got {obs_dim}")
     critic = actor_critic.critic
+    critic_kind = 0
     if isinstance(critic, DenseLayerCritic):
         critic_bins = 1
     elif isinstance(critic, DreamerV3Critic):
@@ -129,14 +132,19 @@ def compile_arch(actor_critic: ActorCritic, obs_dim: int, compute_dtype) -> MlpA
         if critic_bins < 3 or critic_bins % 2 != 1:
             raise ValueError(f"DreamerV3Critic num_bins must be odd and > 1 (dists.py:131), "
                              f"got {critic_bins}")
+    elif isinstance(critic, HLGaussCritic):
+        critic_bins, critic_kind = int(critic.num_bins), nat.CRITIC_HLGAUSS
+        if critic_bins < 3 or critic_bins % 2 != 1:
+            raise ValueError(f"HLGaussCritic needs an odd number of centers >= 3 (mean() is the "
+                             f"symmetric sum around the middle one), got {critic_bins}")
     else:
         raise NotImplementedError(
-            "fused path supports DenseLayerCritic (models.py:142-154) and DreamerV3Critic "
-            f"(157-174); got {type(critic).__name__}")
+            "fused path supports DenseLayerCritic (models.py:142-154), DreamerV3Critic "
+            f"(157-174) and HLGaussCritic (253-307); got {type(critic).__name__}")
     buckets = _actions_buckets(actor_critic.actor, None)
     arch = MlpArch(obs_dim=int(obs_dim), hidden=net.num_channels, num_layers=net.num_layers,
                    buckets=buckets, dtype=compute_dtype, lstm_hidden=lstm_hidden,
-                   critic_bins=critic_bins)
+                   critic_bins=critic_bins, critic_kind=critic_kind)
     arch.head_cols  # raises when the head does not fit
     return arch
 
@@ -148,7 +156,7 @@ class PolicyImages:
     directly).  Built once: ``sync`` rewrites the images in place, the
     descriptor's pointers never change."""
 
-    def __init__(self, arch, layout, params, obs_est=None):
+    def __init__(self, arch, layout, params, obs_est=None, critic=None):
         H, D, L = arch.hidden, arch.obs_dim, arch.num_layers
         dt, dev = arch.dtype, params.device
         self.w_t, self.w = [], []
@@ -159,13 +167,25 @@ class PolicyImages:
         HC = arch.head_cols
         self.head_t = torch.zeros(HC * H, dtype=dt, device=dev)
         self.head = torch.zeros(H * HC, dtype=dt, device=dev)
-        self.head_b = torch.zeros((HC,), dtype=torch.float32, device=dev)
+        # head bias [HC]; behind it (critic_kind 1) the HLGaussCritic's table
+        # centers[CB], bounds[CB + 1], smoothness, filled here once (sync
+        # rewrites the HC biases only)
+        CB = arch.critic_bins
+        tail = 2 * CB + 2 if arch.critic_kind == nat.CRITIC_HLGAUSS else 0
+        self.head_b = torch.zeros((HC + tail,), dtype=torch.float32, device=dev)
+        if tail:
+            if critic is None or critic.centers.shape != (CB,) or critic.bounds.shape != (CB + 1,):
+                raise ValueError("PolicyImages: critic_kind 1 needs the HLGaussCritic's tables")
+            tab = np.concatenate([critic.centers, critic.bounds,
+                                  np.float32([critic.smoothness])]).astype(np.float32)
+            self.head_b[HC:].copy_(torch.from_numpy(tab))
         d = nat.MlpPolicy()
         d.dtype = nat.dtype_code(dt)
         d.obs_dim = D
         d.hidden = H
         d.num_layers = L
         d.critic_bins = arch.critic_bins
+        d.critic_kind = arch.critic_kind
         d.actions = nat.action_layout(arch.buckets)
         for l in range(L):
             d.w_t[l] = self.w_t[l].data_ptr()
@@ -235,7 +255,8 @@ class PolicyState:
             self.obs_est[1:3] = 1.0
             self.obs_count = torch.zeros(1, dtype=torch.int32, device=self.device)
         # compute-dtype fragment-order images read by the kernels (frag.py)
-        self.images = PolicyImages(arch, self.layout, self.params, self.obs_est)
+        self.images = PolicyImages(arch, self.layout, self.params, self.obs_est,
+                                   actor_critic.critic)
         self.w_t, self.w = self.images.w_t, self.images.w
         self.head_t, self.head, self.head_b = (self.images.head_t, self.images.head,
                                                self.images.head_b)
