@@ -626,6 +626,36 @@ int mlearn_lstm_sync_weights(const mlearn_mlp_policy* policy, const mlearn_lstm*
                              const float* params, mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Entity self-attention core (models.py:59-97 SelfAttention, the trunk of */
+/* EntitySelfAttentionNet models.py:451-540)                               */
+/* ---------------------------------------------------------------------- */
+/* Multi-head dot-product attention without mask or dropout, as flax
+ * dot_product_attention computes it for models.py:59-97 (and the reference's
+ * fused pallas/attention.py mha): per (batch row, head)
+ *   out_i = sum_j softmax_j(scale * q_i . k_j) v_j.
+ * q, k, v, out: contiguous [batch][seq][heads][head_dim] in `dtype` (the
+ * projection output viewed with no transpose), 16-byte aligned; lse:
+ * [batch][heads][seq] f32, the log-sum-exp of the scaled logits, kept for the
+ * backward.  seq 1..32, head_dim 16, 32 or 64, dtype MLEARN_DTYPE_F32 or
+ * MLEARN_DTYPE_BF16; anything else (or a null pointer) is MLEARN_EINVAL before
+ * the device is touched.  One wave per (batch row, head) owns its slices of
+ * every output: deterministic, no atomics.  bf16: matrix-core products with
+ * f32 accumulation, f32 softmax statistics, P rounded to bf16 only as an
+ * operand, outputs rounded once; f32: the exact-f32 matrix-core form. */
+int mlearn_attention_fwd(const void* q, const void* k, const void* v, int32_t dtype,
+                         int64_t batch, int32_t seq, int32_t heads, int32_t head_dim,
+                         float scale, void* out, float* lse, mlearn_stream_t stream);
+/* Its exact gradient (jax.grad through dot_product_attention; the reference's
+ * mha backward): with P = exp(scale * S - lse) recomputed from q, k and lse,
+ *   dV = P^T dO, dP = dO V^T, D_i = dO_i . O_i, dS = P * (dP - D),
+ *   dQ = scale * dS K, dK = scale * dS^T Q.
+ * out / lse are the forward's results; dout, dq, dk, dv have q's layout. */
+int mlearn_attention_bwd(const void* q, const void* k, const void* v, const void* out,
+                         const float* lse, const void* dout, int32_t dtype, int64_t batch,
+                         int32_t seq, int32_t heads, int32_t head_dim, float scale,
+                         void* dq, void* dk, void* dv, mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Synthetic dummy vec-env (test/bench sim plugin, not part of the         */
 /* reference: stands in for the Madrona sim_fns['step'] custom call,       */
 /* rollouts.py:905-936).                                                   */

@@ -240,6 +240,10 @@ _SIGNATURES = {
     "mlearn_lstm_optim_step": (c_int32, [POINTER(MlpPolicy), POINTER(Lstm), POINTER(OptimState),
                                          _P, _S]),
     "mlearn_lstm_sync_weights": (c_int32, [POINTER(MlpPolicy), POINTER(Lstm), _P, _S]),
+    "mlearn_attention_fwd": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int32, c_int32, c_int32,
+                                       c_float, _P, _P, _S]),
+    "mlearn_attention_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
+                                       c_int32, c_float, _P, _P, _P, _S]),
     "mlearn_dummy_env_step": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_uint32, c_uint32,
                                         c_uint32, _P, _P, _P, _S]),
     "mlearn_dummy_env_reset": (c_int32, [_P, c_int64, c_int32, c_uint32, c_uint32, c_uint32, _P,

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import attention as _attention
 from .cfg import DiscreteActionsConfig, canonical_dtype
 
 def orthogonal(scale=1.0):
@@ -42,6 +43,24 @@ def orthogonal(scale=1.0):
 def constant(value):
     def init(rng, shape):
         return np.full(shape, value, dtype=np.float32)
+
+    return init
+
+
+def lecun_normal():
+    """flax default_kernel_init (jax.nn.initializers.lecun_normal): a normal
+    truncated at +-2 sigma with variance 1 / fan_in after truncation, i.e.
+    stddev sqrt(1 / fan_in) / 0.87962566103423978 before it; fan_in is the
+    flattened input width of a kernel of shape (..., fan_out)."""
+
+    def init(rng: np.random.Generator, shape):
+        fan_in = int(np.prod(shape[:-1]))
+        x = rng.standard_normal(shape)
+        bad = np.abs(x) > 2.0
+        while bad.any():  # rejection: 4.6 % of the draws per round
+            x[bad] = rng.standard_normal(int(bad.sum()))
+            bad = np.abs(x) > 2.0
+        return (x * (math.sqrt(1.0 / fan_in) / 0.87962566103423978)).astype(np.float32)
 
     return init
 
@@ -110,6 +129,128 @@ class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU p
         for d, n in zip(self.dense, self.norms):
             x = torch.relu(n(d(x)))
         return x
+
+
+class SelfAttention(nn.Module):  # models.py:59-97 (flax nn.SelfAttention)
+    """Multi-head self-attention over the entity axis: query / key / value
+    projections to qkv_features (split over num_heads, scale 1 / sqrt(head_dim)),
+    dot-product attention without mask or dropout, out projection; all four
+    Dense with bias, lecun_normal kernels and zero biases (flax's defaults).
+    x is [..., entities, features]; leading dims are flattened to rows.
+
+    use_ref is accepted for signature compatibility and has no effect (in the
+    reference it selects flax's attention over the Pallas kernel).
+
+    attention_kernel (class attribute, as PPO.step_kernel): 0 = the library's
+    choice, 1 = the torch composition (matmul, softmax in f32, matmul), 2 =
+    the HIP kernel (NotImplementedError where it does not apply: CPU tensors,
+    fp16, more than 32 entities, a head_dim other than 16 / 32 / 64)."""
+
+    attention_kernel = 0
+
+    def __init__(self, num_heads, qkv_features, out_features, dtype, use_ref=True):
+        super().__init__()
+        self.num_heads = int(num_heads)
+        self.qkv_features = int(qkv_features)
+        self.out_features = int(out_features)
+        if self.qkv_features % self.num_heads != 0:
+            raise ValueError(f"SelfAttention: qkv_features {qkv_features} is not divisible by "
+                             f"num_heads {num_heads}")
+        self.dtype = canonical_dtype(dtype)
+        self.use_ref = use_ref
+        self.query = _Dense(self.qkv_features, True, self.dtype, lecun_normal())
+        self.key = _Dense(self.qkv_features, True, self.dtype, lecun_normal())
+        self.value = _Dense(self.qkv_features, True, self.dtype, lecun_normal())
+        self.out = _Dense(self.out_features, True, self.dtype, lecun_normal())
+
+    def forward(self, x):
+        lead, S = x.shape[:-2], x.shape[-2]
+        rows = x.reshape(-1, S, x.shape[-1])
+        H, D = self.num_heads, self.qkv_features // self.num_heads
+        q, k, v = (p(rows).reshape(rows.shape[0], S, H, D)
+                   for p in (self.query, self.key, self.value))
+        o = _attention.attention(q, k, v, 1.0 / math.sqrt(D), type(self).attention_kernel)
+        return self.out(o.reshape(rows.shape[0], S, H * D)).reshape(*lead, S, self.out_features)
+
+
+def _sorted_leaves(tree, out):
+    """(last key, leaf) of a nested dict in the order jax flattens it: keys
+    sorted at every level."""
+    for key in sorted(tree.keys()):
+        if isinstance(tree[key], dict):
+            _sorted_leaves(tree[key], out)
+        else:
+            out.append((key, tree[key]))
+    return out
+
+
+class _EntityEmbed(nn.Module):  # models.py:463-478: Dense (no bias) -> LayerNorm -> leaky ReLU
+    def __init__(self, features, dtype, dense_init):
+        super().__init__()
+        self.dense = _Dense(features, False, dtype, dense_init)
+        self.norm = LayerNorm(dtype)
+
+    def forward(self, x):
+        return nn.functional.leaky_relu(self.norm(self.dense(x)))
+
+
+class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use entity encoder)
+    """x_tree: a dict of observations with 'self' [..., F_self] and entity
+    groups [..., E_g, F_g] (nested dicts contribute their leaves).  Each
+    group is embedded by its own Dense + LayerNorm ('<key>_embed', created on
+    the first call, leaves in sorted key order as jax flattens a dict), the
+    embeddings are concatenated along the entity axis, self-attended with a
+    residual, mean-pooled and passed through a two-layer feed-forward block."""
+
+    def __init__(self, num_embed_channels, num_out_channels, num_heads, dtype,
+                 dense_init=orthogonal(math.sqrt(2)), embed_concat_self=False):
+        super().__init__()
+        self.num_embed_channels = int(num_embed_channels)
+        self.num_out_channels = int(num_out_channels)
+        self.num_heads = int(num_heads)
+        self.dtype = canonical_dtype(dtype)
+        self.dense_init = dense_init
+        self.embed_concat_self = bool(embed_concat_self)
+        self.embed = nn.ModuleDict()
+        self.attention = SelfAttention(self.num_heads, self.num_embed_channels,
+                                       self.num_out_channels, self.dtype)
+        self.attended_norm = LayerNorm(self.dtype)
+        self.ff_0 = _Dense(self.num_out_channels, False, self.dtype, dense_init)
+        self.ff_norm = LayerNorm(self.dtype)
+        self.ff_1 = _Dense(self.num_out_channels, False, self.dtype, dense_init)
+        self.out_norm = LayerNorm(self.dtype)
+
+    def _embed(self, name, x, seen):
+        if name in seen:
+            raise ValueError(f"EntitySelfAttentionNet: two observation leaves are named {name!r}")
+        seen.add(name)
+        if name not in self.embed:
+            self.embed[name] = _EntityEmbed(self.num_embed_channels, self.dtype, self.dense_init)
+        return self.embed[name](x)
+
+    def forward(self, x_tree, train=False):
+        x_tree = dict(x_tree)
+        x_self = x_tree.pop("self").unsqueeze(-2)
+        seen = set()
+        embedded = [self._embed("self_embed", x_self, seen)]
+        for key, x_entities in _sorted_leaves(x_tree, []):
+            if self.embed_concat_self:
+                x_entities = torch.cat(
+                    [x_entities, x_self.expand(*x_entities.shape[:-1], x_self.shape[-1])], dim=-1)
+            embedded.append(self._embed(f"{key}_embed", x_entities, seen))
+        embedded = torch.cat(embedded, dim=-2)
+
+        attended = self.attention(embedded)
+        if self.num_embed_channels != self.num_out_channels:
+            reps = self.num_out_channels // self.num_embed_channels
+            attended = attended + embedded.repeat(*([1] * (embedded.dim() - 1)), reps)
+        else:
+            attended = attended + embedded
+        attended = self.attended_norm(attended.mean(dim=-2))
+
+        ff = nn.functional.leaky_relu(self.ff_norm(self.ff_0(attended)))
+        ff = nn.functional.leaky_relu(self.ff_1(ff))  # (a transformer block has no activation here)
+        return self.out_norm(attended + ff)
 
 
 def action_groups(cfg):
