@@ -326,7 +326,9 @@ def test_lstm_optimizer_step_and_images(gpu):
     m = np.zeros_like(p)
     v = np.zeros_like(p)
     for step in range(3):
-        g = (rng.standard_normal(p.size) * (0.01 if step != 1 else 1.0)).astype(np.float32)
+        # (norm 0.6 x max_grad_norm: unclipped; the middle step is clipped)
+        g = (rng.standard_normal(p.size)
+             * (0.6 * 0.5 / np.sqrt(p.size) if step != 1 else 1.0)).astype(np.float32)
         ts.grads.copy_(torch.from_numpy(g))
         ts.optimizer_step(ps)
         p, m, v, _ = lref.optimizer_step(p, g.astype(np.float64), m, v, step, lay, init_norms,

@@ -8,7 +8,8 @@ parameters, Adam moments, the step counter and every compute image, over
 several steps (one with a clipped norm), with the norm partials taken from
 the gradient reduction (world 1) or formed in the launch (the all-reduced
 gradient, world > 1), on MLP and LSTM layouts.  The oracle comparisons of
-the optimizer (tests/test_gpu_policy.py, tests/test_gpu_lstm.py) and of
+the optimizer (tests/test_gpu_optim_oracle.py with the Adam moments and the
+norm, tests/test_gpu_policy.py, tests/test_gpu_lstm.py) and of
 every full update run on the split launches, the library's default (the
 fused launch measured no faster)."""
 
@@ -78,7 +79,8 @@ def test_fused_optimizer_bit_identical(gpu, kind, dtype, D, H, L, CB, with_parti
     ts = [_train_state(ps[0], 1, parts), _train_state(ps[1], 2, parts)]
     rng = np.random.default_rng(6)
     for step in range(4):
-        g = torch.from_numpy((rng.standard_normal(n) * (0.01 if step != 1 else 1.0))
+        # (norm 0.6 x max_grad_norm: unclipped; step 1 is the clipped one)
+        g = torch.from_numpy((rng.standard_normal(n) * (0.6 * 0.5 / np.sqrt(n) if step != 1 else 1.0))
                              .astype(np.float32)).to(gpu)
         if parts is not None:  # per-64-parameter partials of g^2, as the gradient reduction
             gp = torch.nn.functional.pad(g.double(), (0, parts.numel() * 64 - n))

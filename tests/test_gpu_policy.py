@@ -231,6 +231,9 @@ def test_minibatch_grad(gpu, mode, dtype, D, H, L, CB, bptt, mb):
 
 
 def test_optimizer_step(gpu):
+    """Three steps, the middle one clipped: the others have norm 0.6 x
+    max_grad_norm, so both branches of clip_by_global_norm run.  Parameters
+    only; tests/test_gpu_optim_oracle.py holds the moments and the norm."""
     from madrona_learn.train_state import PolicyTrainState
     from madrona_learn.ppo import PPOHyperParams
     ps = make_policy_state(gpu, 64, 256, 2, torch.float32, seed=4)
@@ -246,7 +249,8 @@ def test_optimizer_step(gpu):
     v = np.zeros_like(p)
     init_norms = ps.init_norms.cpu().numpy().astype(np.float64)
     for step in range(3):
-        g = (rng.standard_normal(p.size) * (0.01 if step != 1 else 1.0)).astype(np.float32)
+        g = (rng.standard_normal(p.size)
+             * (0.6 * 0.5 / np.sqrt(p.size) if step != 1 else 1.0)).astype(np.float32)
         ts.grads.copy_(torch.from_numpy(g))
         ts.optimizer_step(ps)
         p, m, v, gn = ref.optimizer_step(p, g.astype(np.float64), m, v, step, lay, init_norms,
