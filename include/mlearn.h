@@ -656,6 +656,64 @@ int mlearn_attention_bwd(const void* q, const void* k, const void* v, const void
                          void* dq, void* dk, void* dv, mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Continuous actions (dists.py:211-284 ContinuousActionDistributions);    */
+/* the torch path's sampler and action_stats (additive exports)            */
+/* ---------------------------------------------------------------------- */
+/* G groups of D dimensions each, flat column e = g * D + d of A = G * D <=
+ * 1024 columns; group g's std lies in [std_min[g], std_max[g]], 0 < min <=
+ * max.  Per column, in f32 from the raw inputs x (mean) and y (std):
+ *   m = tanh(x), s = (hi - lo) sigmoid(y + 2) + lo, z = (a - m) / s,
+ *   logp = -z^2 / 2 - ln s - ln(2 pi) / 2, ent = ln s + ln(2 pi) / 2 + 1/2
+ * (per dimension, not summed over D).  means / stds: [rows][A] in `dtype`
+ * (MLEARN_DTYPE_F32 / MLEARN_DTYPE_BF16) with row strides ld_means, ld_stds
+ * >= A in elements (the two halves of one [rows][2A] Dense output pass
+ * without a copy); actions, log_probs, entropies and incoming gradients are
+ * contiguous f32 [rows][A].  Bad arguments (a null pointer, G, D or A out of
+ * range, ld < A, another dtype, a group without 0 < std_min <= std_max) are
+ * MLEARN_EINVAL before the device is touched.  Nothing is allocated, no
+ * atomics, the results do not depend on the grid. */
+typedef struct mlearn_continuous_layout {
+    int32_t num_groups, num_dims;
+    float std_min[MLEARN_MAX_GROUPS], std_max[MLEARN_MAX_GROUPS];
+} mlearn_continuous_layout;
+
+/* sample (sample != 0): a = fmaf(z, s, m) with z ~ N(0, 1) by Box-Muller over
+ * Philox4x32-10: for env row n (global id env_offset + n), step *step_ctr +
+ * step (step_ctr: device uint64, may be NULL) and column block b = e >> 2 the
+ * counter is {env, 0x80000000 | b, step lo, step hi}, key {k0, k1}; words
+ * (w0, w1) give columns 4b, 4b + 1 as r cos(2 pi u2), r sin(2 pi u2), r =
+ * sqrt(-2 ln u1), words (w2, w3) columns 4b + 2, 4b + 3.  z is bit-identical
+ * to mlearn_continuous_sample_host.  best (sample == 0): a = tanh(x).
+ * log_probs may be NULL. */
+int mlearn_continuous_sample(const void* means, int64_t ld_means, const void* stds,
+                             int64_t ld_stds, int32_t dtype, mlearn_continuous_layout layout,
+                             int64_t N, uint32_t k0, uint32_t k1, const uint64_t* step_ctr,
+                             uint64_t step, uint32_t env_offset, int32_t sample,
+                             float* actions_f32, float* log_probs_f32, mlearn_stream_t stream);
+/* The same on host memory, without a GPU (step_ctr: a host pointer). */
+int mlearn_continuous_sample_host(const void* means, int64_t ld_means, const void* stds,
+                                  int64_t ld_stds, int32_t dtype,
+                                  mlearn_continuous_layout layout, int64_t N, uint32_t k0,
+                                  uint32_t k1, const uint64_t* step_ctr, uint64_t step,
+                                  uint32_t env_offset, int32_t sample, float* actions_f32,
+                                  float* log_probs_f32);
+/* action_stats (dists.py:260-284): log_probs and entropies of the given actions. */
+int mlearn_continuous_stats(const void* means, int64_t ld_means, const void* stds,
+                            int64_t ld_stds, int32_t dtype, mlearn_continuous_layout layout,
+                            int64_t R, const float* actions, float* log_probs, float* entropies,
+                            mlearn_stream_t stream);
+/* Its gradient, m, s and z recomputed from the inputs (the forward saves
+ * nothing); either incoming gradient may be NULL (zero).  d_means / d_stds in
+ * `dtype` with row strides ld_dm, ld_ds >= A, each rounded once:
+ *   dx = g_lp (z / s)(1 - m^2)
+ *   dy = (g_lp (z^2 - 1) / s + g_ent / s)(hi - lo) sigma (1 - sigma). */
+int mlearn_continuous_stats_bwd(const void* means, int64_t ld_means, const void* stds,
+                                int64_t ld_stds, int32_t dtype, mlearn_continuous_layout layout,
+                                int64_t R, const float* actions, const float* g_log_probs,
+                                const float* g_entropies, void* d_means, int64_t ld_dm,
+                                void* d_stds, int64_t ld_ds, mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Synthetic dummy vec-env (test/bench sim plugin, not part of the         */
 /* reference: stands in for the Madrona sim_fns['step'] custom call,       */
 /* rollouts.py:905-936).                                                   */

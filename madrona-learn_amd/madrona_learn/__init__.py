@@ -12,7 +12,7 @@ from .actor_critic import (ActorCritic, Backbone, BackboneEncoder, BackboneSepar
                            BackboneShared, RecurrentBackboneEncoder)
 from .cfg import (ContinuousActionsConfig, DiscreteActionsConfig, EvalConfig, ParamExplore,
                   PBTConfig, TrainConfig)
-from .dists import DiscreteActionDistributions, PhiloxKey
+from .dists import ContinuousActionDistributions, DiscreteActionDistributions, PhiloxKey
 from .eval import eval_load_ckpt, eval_policies
 from .observations import (ObservationsCaster, ObservationsEMANormalizer,
                            ObservationsPreprocessNoop)
@@ -30,7 +30,7 @@ __all__ = [
     "init_training", "stop_training", "train", "TrainHooks", "TrainingManager",
     "DiscreteActionsConfig", "ContinuousActionsConfig", "TrainConfig", "PBTConfig",
     "ParamExplore", "EvalConfig", "eval_load_ckpt", "eval_policies", "TrainStateManager", "models", "rnn", "Policy",
-    "DiscreteActionDistributions", "PhiloxKey", "ObservationsEMANormalizer",
+    "DiscreteActionDistributions", "ContinuousActionDistributions", "PhiloxKey", "ObservationsEMANormalizer",
     "ObservationsCaster", "ObservationsPreprocessNoop", "ActorCritic", "BackboneEncoder",
     "RecurrentBackboneEncoder", "Backbone", "BackboneShared", "BackboneSeparate", "PPOConfig",
     "profile", "TensorboardWriter", "pbt",

@@ -33,6 +33,11 @@ class ActionLayout(Structure):
                 ("offsets", c_int32 * (MAX_GROUPS + 1))]
 
 
+class ContinuousLayout(Structure):  # mlearn_continuous_layout
+    _fields_ = [("num_groups", c_int32), ("num_dims", c_int32),
+                ("std_min", c_float * MAX_GROUPS), ("std_max", c_float * MAX_GROUPS)]
+
+
 class MlpPolicy(Structure):
     _fields_ = [("dtype", c_int32), ("obs_dim", c_int32), ("hidden", c_int32),
                 ("num_layers", c_int32), ("critic_bins", c_int32), ("actions", ActionLayout),
@@ -244,6 +249,16 @@ _SIGNATURES = {
                                        c_float, _P, _P, _S]),
     "mlearn_attention_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
                                        c_int32, c_float, _P, _P, _P, _S]),
+    "mlearn_continuous_sample": (c_int32, [_P, c_int64, _P, c_int64, c_int32, ContinuousLayout,
+                                           c_int64, c_uint32, c_uint32, _P, c_uint64, c_uint32,
+                                           c_int32, _P, _P, _S]),
+    "mlearn_continuous_sample_host": (c_int32, [_P, c_int64, _P, c_int64, c_int32,
+                                                ContinuousLayout, c_int64, c_uint32, c_uint32, _P,
+                                                c_uint64, c_uint32, c_int32, _P, _P]),
+    "mlearn_continuous_stats": (c_int32, [_P, c_int64, _P, c_int64, c_int32, ContinuousLayout,
+                                          c_int64, _P, _P, _P, _S]),
+    "mlearn_continuous_stats_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int32, ContinuousLayout,
+                                              c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, _S]),
     "mlearn_dummy_env_step": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_uint32, c_uint32,
                                         c_uint32, _P, _P, _P, _S]),
     "mlearn_dummy_env_reset": (c_int32, [_P, c_int64, c_int32, c_uint32, c_uint32, c_uint32, _P,
@@ -281,7 +296,12 @@ def lib():
     # one the library binds to: one runtime, shared streams.
     h = ctypes.CDLL(LIB_PATH)
     for name, (res, args) in _SIGNATURES.items():
-        fn = getattr(h, name)
+        try:
+            fn = getattr(h, name)
+        except AttributeError:
+            raise RuntimeError(
+                f"madrona_learn: {LIB_PATH} does not export {name} (a stale build); rebuild it "
+                "with `make -C madrona-learn_amd`") from None
         fn.restype = res
         fn.argtypes = args
     v = h.mlearn_abi_version()
@@ -338,6 +358,22 @@ def action_layout(buckets):
     lay.num_logits = off
     if off + 1 > HEAD_COLS_MAX:
         raise ValueError(f"at most {HEAD_COLS_MAX - 1} total logits supported, got {off}")
+    return lay
+
+
+def continuous_layout(cfgs):
+    """mlearn_continuous_layout of a list of ContinuousActionsConfig (one per
+    group, all with the same num_dims)."""
+    cfgs = list(cfgs)
+    if not 1 <= len(cfgs) <= MAX_GROUPS:
+        raise ValueError(f"1..{MAX_GROUPS} continuous action groups supported, got {len(cfgs)}")
+    dims = {int(c.num_dims) for c in cfgs}
+    if len(dims) != 1:
+        raise ValueError(f"continuous action groups must share one num_dims, got {sorted(dims)}")
+    lay = ContinuousLayout()
+    lay.num_groups, lay.num_dims = len(cfgs), dims.pop()
+    for g, c in enumerate(cfgs):
+        lay.std_min[g], lay.std_max[g] = float(c.stddev_min), float(c.stddev_max)
     return lay
 
 

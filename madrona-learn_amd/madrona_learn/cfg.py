@@ -19,7 +19,8 @@ class DiscreteActionsConfig:  # cfg.py:9-11
 
 
 @dataclass(frozen=True)
-class ContinuousActionsConfig:  # cfg.py:13-17 (not on the accelerated path)
+class ContinuousActionsConfig:  # cfg.py:13-17 (trains on the torch path: HIP sampler and
+    # action_stats kernels around the user's modules; no fused head)
     stddev_min: float
     stddev_max: float
     num_dims: int

@@ -97,6 +97,152 @@ class DiscreteActionDistributions:
         return out
 
 
+_HALF_LN_2PI = 0.5 * math.log(2.0 * math.pi)
+_BOUNDS = {}  # ContinuousActionDistributions._bounds
+
+
+def _kernel_choice(kernel):
+    if kernel in (0, None, "hip", "torch"):
+        return kernel or 0
+    raise ValueError(f"kernel must be 0, 'hip' or 'torch', got {kernel!r}")
+
+
+class _ContinuousStats(torch.autograd.Function):
+    """ContinuousActionDistributions.action_stats on mlearn_continuous_stats,
+    its gradient on mlearn_continuous_stats_bwd (m, s, z recomputed from the
+    raw inputs: only the inputs are saved).  raw_means / raw_stds: [R, A]
+    views with unit column stride (e.g. the halves of one Dense output)."""
+
+    @staticmethod
+    def forward(ctx, raw_means, raw_stds, actions, layout):
+        R, A = raw_means.shape
+        acts = actions.to(torch.float32).reshape(R, A).contiguous()
+        logp = torch.empty((R, A), dtype=torch.float32, device=raw_means.device)
+        ent = torch.empty_like(logp)
+        nat.check(nat.lib().mlearn_continuous_stats(
+            raw_means.data_ptr(), raw_means.stride(0), raw_stds.data_ptr(), raw_stds.stride(0),
+            nat.dtype_code(raw_means.dtype), layout, R, nat.ptr(acts), nat.ptr(logp),
+            nat.ptr(ent), nat.stream_handle()), "continuous_stats")
+        ctx.save_for_backward(raw_means, raw_stds, acts)
+        ctx.layout = layout
+        return logp, ent
+
+    @staticmethod
+    def backward(ctx, g_logp, g_ent):
+        raw_means, raw_stds, acts = ctx.saved_tensors
+        R, A = raw_means.shape
+        g_logp = None if g_logp is None else g_logp.to(torch.float32).contiguous()
+        g_ent = None if g_ent is None else g_ent.to(torch.float32).contiguous()
+        d_means = torch.empty((R, A), dtype=raw_means.dtype, device=raw_means.device)
+        d_stds = torch.empty_like(d_means)
+        nat.check(nat.lib().mlearn_continuous_stats_bwd(
+            raw_means.data_ptr(), raw_means.stride(0), raw_stds.data_ptr(), raw_stds.stride(0),
+            nat.dtype_code(raw_means.dtype), ctx.layout, R, nat.ptr(acts), nat.ptr(g_logp),
+            nat.ptr(g_ent), nat.ptr(d_means), A, nat.ptr(d_stds), A, nat.stream_handle()),
+            "continuous_stats_bwd")
+        return d_means, d_stds, None, None
+
+
+class ContinuousActionDistributions:  # dists.py:211-284
+    """Diagonal Gaussians over G action groups of D dimensions each: raw
+    ``means`` / ``stds`` [..., G, D] (tanh mean, std bounded to the group's
+    [stddev_min, stddev_max] by a sigmoid); actions, log_probs and entropies
+    are [..., G, D], per dimension (not summed over D), as the reference's
+    PPO ratio takes them.
+
+    ``kernel``: 0 (default) / "hip" run the HIP kernels of csrc/continuous.hip
+    on GPU tensors; "torch" evaluates action_stats as a torch composition of
+    the same formulas (also what CPU tensors get).  Sampling always draws its
+    normals from the Philox counter stream (DESIGN.md "RNG"): the HIP sampler
+    on the GPU, the library's host sampler for CPU tensors."""
+
+    kernel = 0  # the default of instances created without kernel=
+
+    def __init__(self, cfgs, means, stds, kernel=None):
+        self.cfgs = list(cfgs)
+        self.means = means
+        self.stds = stds
+        if kernel is not None:
+            self.kernel = _kernel_choice(kernel)
+        self._layout = nat.continuous_layout(self.cfgs)
+        G, D = self._layout.num_groups, self._layout.num_dims
+        if tuple(means.shape[-2:]) != (G, D) or means.shape != stds.shape:
+            raise ValueError(f"means / stds must be [..., {G}, {D}], got {tuple(means.shape)} and "
+                             f"{tuple(stds.shape)}")
+
+    def _rows(self, x):
+        """x [..., G, D] as a [R, A] view with unit column stride (a copy
+        only where no such view exists), in a dtype the kernels read."""
+        G, D = self._layout.num_groups, self._layout.num_dims
+        if x.dtype not in (torch.float32, torch.bfloat16):
+            x = x.float()  # dists.py:221 upcasts to f32 anyway
+        x = x.reshape(-1, G * D)
+        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < G * D):
+            x = x.contiguous()
+        return x
+
+    def _bounds(self, ref):
+        """(lo, hi) as [G, 1] f32 tensors on ref's device, made once per
+        (device, bounds): no host copy inside a captured update."""
+        vals = tuple((float(c.stddev_min), float(c.stddev_max)) for c in self.cfgs)
+        k = (ref.device, vals)
+        if k not in _BOUNDS:
+            t = torch.tensor(vals, dtype=torch.float32).to(ref.device)
+            _BOUNDS[k] = (t[:, 0:1].contiguous(), t[:, 1:2].contiguous())
+        return _BOUNDS[k]
+
+    def _sample(self, key: PhiloxKey, sample):
+        m, s = self._rows(self.means.detach()), self._rows(self.stds.detach())
+        if m.dtype != s.dtype:
+            m, s = m.float(), s.float()
+        N, A = m.shape
+        actions = torch.empty((N, A), dtype=torch.float32, device=m.device)
+        logp = torch.empty_like(actions) if sample else None
+        L = nat.lib()
+        ld = lambda x: x.stride(0) if N > 1 else A  # noqa: E731
+        if m.is_cuda:
+            nat.check(L.mlearn_continuous_sample(
+                m.data_ptr(), ld(m), s.data_ptr(), ld(s), nat.dtype_code(m.dtype), self._layout, N,
+                key.k0, key.k1, None if key.ctr is None else nat.ptr(key.ctr), key.step,
+                key.env_offset, 1 if sample else 0, nat.ptr(actions), nat.ptr(logp),
+                nat.stream_handle()), "continuous_sample")
+        else:
+            ctr = None if key.ctr is None else key.ctr.view(torch.int64)[:1].contiguous()
+            nat.check(L.mlearn_continuous_sample_host(
+                m.data_ptr(), ld(m), s.data_ptr(), ld(s), nat.dtype_code(m.dtype), self._layout, N,
+                key.k0, key.k1, None if ctr is None else ctr.data_ptr(), key.step,
+                key.env_offset, 1 if sample else 0, actions.data_ptr(),
+                None if logp is None else logp.data_ptr()), "continuous_sample_host")
+        shape = self.means.shape
+        return actions.reshape(shape), (logp.reshape(shape) if logp is not None else None)
+
+    def sample(self, prng_key: PhiloxKey):  # dists.py:223-249
+        return self._sample(prng_key, True)
+
+    def best(self):  # dists.py:251-258
+        return self._sample(PhiloxKey(0, 0), False)[0]
+
+    def _stats_torch(self, all_actions):
+        lo, hi = self._bounds(self.means)
+        mean = torch.tanh(self.means.float())
+        std = (hi - lo) * torch.sigmoid(self.stds.float() + 2.0) + lo
+        z = (all_actions.float().reshape(mean.shape) - mean) / std
+        ls = torch.log(std)
+        return -0.5 * z * z - ls - _HALF_LN_2PI, ls + (_HALF_LN_2PI + 0.5)
+
+    def action_stats(self, all_actions: torch.Tensor):  # dists.py:260-284
+        if self.kernel == "torch" or not self.means.is_cuda:
+            if self.kernel == "hip":
+                raise NotImplementedError("ContinuousActionDistributions: kernel='hip' needs GPU "
+                                          "tensors")
+            return self._stats_torch(all_actions)
+        m, s = self._rows(self.means), self._rows(self.stds)
+        if m.dtype != s.dtype:
+            m, s = m.float(), s.float()
+        logp, ent = _ContinuousStats.apply(m, s, all_actions, self._layout)
+        return logp.reshape(self.means.shape), ent.reshape(self.means.shape)
+
+
 def _symexp(x):  # utils.py:39-40
     return torch.sign(x) * torch.expm1(torch.abs(x))
 

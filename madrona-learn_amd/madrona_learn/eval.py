@@ -153,7 +153,7 @@ def eval_policies(dev, eval_cfg: EvalConfig, sim_fns: Dict[str, Callable], polic
     ``clear_fitness`` is off (default 1500 each).  Returns the Elo tensor
     ([policies + custom ids]) of a competitive evaluation, else the list of
     per-policy MovingEpisodeScore."""
-    from .models import action_groups
+    from .models import _discrete_only, action_groups
     from .pbt import pbt_update_elo, pbt_update_fitness
     from .train import _split_seed
     device = torch.device(dev) if not isinstance(dev, torch.device) else dev
@@ -202,7 +202,7 @@ def eval_policies(dev, eval_cfg: EvalConfig, sim_fns: Dict[str, Callable], polic
     step_fn = sim_fns["step"]
     prefix = getattr(policy.actor_critic.backbone, "prefix", None) or \
         (lambda x, train=False: x)
-    groups = action_groups(eval_cfg.actions)
+    groups = _discrete_only(action_groups(eval_cfg.actions), "eval_policies (fused-only)")
     sample = not eval_cfg.use_deterministic_policy
     key = _split_seed(0, 1) if sample else (0, 0)  # the rollout stream of seed 0 (PRNGKey(0))
     counters = torch.zeros(8, dtype=torch.int64, device=device)

@@ -20,6 +20,11 @@ autograd, while everything around them stays on the HIP kernels of
   ``zscore_data`` (mlearn_adv_stats / _finish, all-reduced under DP);
 * ``action_stats`` (mlearn_action_stats_f32 forward; its backward through
   the softmax in torch);
+* continuous actions (``TrainConfig.actions`` of ContinuousActionsConfig, an
+  actor returning ``ContinuousActionDistributions``): Box-Muller sampling over
+  the Philox counter stream (mlearn_continuous_sample) and the distribution's
+  own differentiable ``action_stats`` (mlearn_continuous_stats / _stats_bwd);
+  the store's actions are then f32 [T][N][G D], log-probs per dimension;
 * clip_by_global_norm + Adam + normalize_params / normalize_layernorms over
   the flat parameter vector (mlearn_flat_optim_step).
 
@@ -55,7 +60,7 @@ from . import _native as nat
 from .dists import (DiscreteActionDistributions, HLGaussDist, PhiloxKey,
                     SymExpTwoHotDistribution)
 from .dynamic_scale import DynamicScale
-from .models import LayerNorm, _Dense, action_groups
+from .models import LayerNorm, _Dense, action_groups, continuous_groups
 from .observations import ObservationsPreprocess, _wrap
 from .pbt import MovingEpisodeScore
 from .ppo import _base
@@ -71,6 +76,9 @@ class GenericArch:
     dtype: torch.dtype      # compute dtype (the store's observation dtype)
     critic_bins: int = 1    # 1: scalar critic; > 1: SymExpTwoHotDistribution logits
     lstm_hidden: int = 0
+    # continuous actions: (G, D) of the actor's [..., G, D] head (buckets is
+    # then empty); None: discrete buckets
+    continuous: tuple = None
 
     @property
     def num_logits(self):
@@ -78,7 +86,22 @@ class GenericArch:
 
     @property
     def num_groups(self):
-        return len(self.buckets)
+        return len(self.buckets) if self.continuous is None else self.continuous[0]
+
+    @property
+    def action_kind(self):
+        return "discrete" if self.continuous is None else "continuous"
+
+    @property
+    def action_cols(self):
+        """Columns of the stored actions / log-probs: one per discrete action,
+        G D for continuous groups."""
+        return len(self.buckets) if self.continuous is None else \
+            self.continuous[0] * self.continuous[1]
+
+    @property
+    def action_dtype(self):
+        return torch.int32 if self.continuous is None else torch.float32
 
 
 class ObsCodec:
@@ -239,8 +262,15 @@ class TorchPolicyState:
         self.critic_form = "hlgauss" if isinstance(crit, HLGaussDist) else \
             ("two-hot" if self.critic_bins > 1 else "scalar")
         self.codec = ObsCodec(pre)
-        self.arch = GenericArch(obs_dim=self.codec.width, buckets=tuple(int(b) for b in buckets),
-                                dtype=compute_dtype, critic_bins=self.critic_bins)
+        # the action kind follows what the actor's head returned: f32 [1, G, D]
+        # actions of a ContinuousActionDistributions, else int32 [1, K] buckets
+        acts = out["actions"]
+        cont = (int(acts.shape[-2]), int(acts.shape[-1])) \
+            if acts.is_floating_point() and acts.dim() == 3 else None
+        self.arch = GenericArch(obs_dim=self.codec.width,
+                                buckets=() if cont else tuple(int(b) for b in buckets),
+                                dtype=compute_dtype, critic_bins=self.critic_bins,
+                                continuous=cont)
         named = [(n, p) for n, p in self.actor_critic.named_parameters()]
         total = int(sum(p.numel() for _, p in named))
         self.params = torch.zeros(total, dtype=torch.float32, device=device)
@@ -640,9 +670,21 @@ class TorchPPO:
             b.vn_rec = torch.zeros((b.E, b.num_mb, 8), dtype=torch.float32, device=dev)
             b.adv_sums = torch.zeros((b.E, 4 * b.num_mb), dtype=torch.float64, device=dev)
         self.groups = action_groups(cfg.actions)
-        if tuple(x for _, g in self.groups for x in g) != tuple(ps.arch.buckets):
+        self.cont = continuous_groups(self.groups)
+        if self.cont is not None:
+            want = (len(self.cont), int(self.cont[0].num_dims))
+            if ps.arch.continuous != want:
+                raise ValueError(f"TrainConfig.actions has {want[0]} continuous groups of "
+                                 f"{want[1]} dims but the actor's head returned "
+                                 f"{ps.arch.continuous or 'discrete actions'}")
+            head = getattr(ps.actor_critic.actor, "cfgs", None)
+            if head is not None and list(head) != list(self.cont):
+                raise ValueError(f"TrainConfig.actions {self.cont} does not match the actor's "
+                                 f"head {list(head)}")
+        elif ps.arch.continuous is not None or \
+                tuple(x for _, g in self.groups for x in g) != tuple(ps.arch.buckets):
             raise ValueError(f"TrainConfig.actions {self.groups} does not match the actor's "
-                             f"head {ps.arch.buckets}")
+                             f"head {ps.arch.continuous or ps.arch.buckets}")
         ec = algo.entropy_coef
         self.ecoef = [float(_base(ec[n] if isinstance(ec, dict) else ec)) for n, _ in self.groups]
         self.clip = float(algo.clip_coef)
@@ -694,8 +736,15 @@ class TorchPPO:
                                                 mbd["dones"][..., None], obs, train=True)
         dists = act_f(feats_a, train=True) if _takes_train(act_f) else act_f(feats_a)
         crit = ac.critic(feats_c, train=True) if _takes_train(ac.critic) else ac.critic(feats_c)
-        logp, ent = action_stats_autograd(dists, mbd["actions"].reshape(T * M, -1))
-        K = logp.shape[-1]
+        if self.cont is not None:
+            # the distribution's own differentiable action_stats, per dimension
+            # (dists.py:260-284): [T, M, G, D] -> the G D stored columns; the
+            # ratio, clip and min below are per column, the advantage broadcast
+            # over them (ppo.py:145-164)
+            logp, ent = dists.action_stats(mbd["actions"].reshape(dists.means.shape))
+        else:
+            logp, ent = action_stats_autograd(dists, mbd["actions"].reshape(T * M, -1))
+        K = logp.numel() // (T * M)
         logp = logp.reshape(T, M, K)
         ent = ent.reshape(T, M, K)
         adv = mbd["advantages"].float()
@@ -712,8 +761,8 @@ class TorchPPO:
         action_obj = 0.0
         entropy_term = 0.0
         off = 0
-        for (name, g), c in zip(self.groups, self.ecoef):
-            k = len(g)
+        for grp, c in zip(self.groups, self.ecoef):
+            k = grp.cols
             action_obj = action_obj + obj[..., off:off + k].mean()
             entropy_term = entropy_term + c * ent[..., off:off + k].mean()
             off += k

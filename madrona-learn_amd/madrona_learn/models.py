@@ -20,7 +20,7 @@ import torch
 from torch import nn
 
 from . import attention as _attention
-from .cfg import DiscreteActionsConfig, canonical_dtype
+from .cfg import ContinuousActionsConfig, DiscreteActionsConfig, canonical_dtype
 
 def orthogonal(scale=1.0):
     """jax.nn.initializers.orthogonal restated (column/row orthonormal * scale)
@@ -253,17 +253,68 @@ class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use
         return self.out_norm(attended + ff)
 
 
+class ActionGroup(tuple):
+    """One key of TrainConfig.actions as (name, spec): spec is the bucket list
+    of a DiscreteActionsConfig, or the ContinuousActionsConfig itself.
+    ``kind`` is "discrete" / "continuous", ``cols`` the group's columns of the
+    stored actions and log-probs (len(buckets) or num_dims)."""
+
+    def __new__(cls, name, spec):
+        return super().__new__(cls, (name, spec))
+
+    def __getnewargs__(self):  # copy.deepcopy of a module holding groups (populations), pickle
+        return (self[0], self[1])
+
+    @property
+    def kind(self):
+        return "continuous" if isinstance(self[1], ContinuousActionsConfig) else "discrete"
+
+    @property
+    def cols(self):
+        return int(self[1].num_dims) if self.kind == "continuous" else len(self[1])
+
+
 def action_groups(cfg):
-    """[(name, buckets)] of a DiscreteActionsConfig or of a dict name ->
-    DiscreteActionsConfig (TrainConfig.actions, cfg.py:73)."""
-    if isinstance(cfg, DiscreteActionsConfig):
-        return [("actions", list(cfg.actions_num_buckets))]
+    """[ActionGroup(name, spec)] of one actions config or of a dict name ->
+    config (TrainConfig.actions, cfg.py:73): all DiscreteActionsConfig (spec =
+    its buckets) or all ContinuousActionsConfig (spec = the config, every
+    group with the same num_dims: the reference's [..., G, D] tensors)."""
+    if isinstance(cfg, (DiscreteActionsConfig, ContinuousActionsConfig)):
+        cfg = {"actions": cfg}
     out = []
     for k, v in cfg.items():
-        if not isinstance(v, DiscreteActionsConfig):
-            raise NotImplementedError(f"action group {k!r}: only discrete actions are supported")
-        out.append((k, list(v.actions_num_buckets)))
+        if isinstance(v, DiscreteActionsConfig):
+            out.append(ActionGroup(k, list(v.actions_num_buckets)))
+        elif isinstance(v, ContinuousActionsConfig):
+            out.append(ActionGroup(k, v))
+        else:
+            raise TypeError(f"action group {k!r}: expected a DiscreteActionsConfig or a "
+                            f"ContinuousActionsConfig, got {type(v).__name__}")
+    kinds = {g.kind for g in out}
+    if len(kinds) > 1:
+        raise NotImplementedError(
+            "TrainConfig.actions mixes discrete and continuous action groups "
+            f"({', '.join(f'{g[0]}: {g.kind}' for g in out)}): a mix is not supported")
+    if kinds == {"continuous"}:
+        dims = sorted({g.cols for g in out})
+        if len(dims) > 1:
+            raise ValueError(f"continuous action groups must share one num_dims, got {dims}")
     return out
+
+
+def continuous_groups(groups):
+    """The ContinuousActionsConfig list of action_groups' result, or None for
+    discrete groups."""
+    if groups and groups[0].kind == "continuous":
+        return [g[1] for g in groups]
+    return None
+
+
+def _discrete_only(groups, what):
+    if continuous_groups(groups) is not None:
+        raise NotImplementedError(f"{what}: continuous actions run on the torch path only "
+                                  "(DenseLayerContinuousActor, generic.py)")
+    return groups
 
 
 class DenseLayerDiscreteActor(nn.Module):  # models.py:122-139
@@ -276,13 +327,44 @@ class DenseLayerDiscreteActor(nn.Module):  # models.py:122-139
         self.cfg = cfg
         self.dtype = canonical_dtype(dtype)
         self.weight_init = weight_init
-        self.groups = action_groups(cfg)
+        self.groups = _discrete_only(action_groups(cfg), "DenseLayerDiscreteActor")
         self.buckets = [b for _, g in self.groups for b in g]
         self.impl = _Dense(sum(self.buckets), True, self.dtype, weight_init)
 
     def forward(self, features, train=False):
         from .dists import DiscreteActionDistributions
         return DiscreteActionDistributions(self.buckets, self.impl(features))
+
+
+class DenseLayerContinuousActor(nn.Module):
+    """This build's addition (the reference ships ContinuousActionDistributions
+    but no actor module for it): one Dense of width 2 G D whose first half are
+    the raw means and second half the raw stds of G groups of D dimensions.
+    cfg: one ContinuousActionsConfig, or a dict of them keyed like
+    TrainConfig.actions (groups in dict order, one num_dims for all).
+    kernel: ContinuousActionDistributions' switch (None: its default)."""
+
+    def __init__(self, cfg, dtype, weight_init=orthogonal(0.01), kernel=None):
+        super().__init__()
+        self.cfg = cfg
+        self.dtype = canonical_dtype(dtype)
+        self.weight_init = weight_init
+        self.kernel = kernel
+        self.groups = action_groups(cfg)
+        self.cfgs = continuous_groups(self.groups)
+        if self.cfgs is None:
+            raise TypeError("DenseLayerContinuousActor takes ContinuousActionsConfig groups")
+        self.num_groups, self.num_dims = len(self.cfgs), int(self.cfgs[0].num_dims)
+        self.impl = _Dense(2 * self.num_groups * self.num_dims, True, self.dtype, weight_init)
+
+    def forward(self, features, train=False):
+        from .dists import ContinuousActionDistributions
+        y = self.impl(features)
+        A = self.num_groups * self.num_dims
+        shape = (*y.shape[:-1], self.num_groups, self.num_dims)
+        # (views of the Dense output: the kernels read the halves in place)
+        return ContinuousActionDistributions(self.cfgs, y[..., :A].reshape(shape),
+                                             y[..., A:].reshape(shape), kernel=self.kernel)
 
 
 class DenseLayerCritic(nn.Module):  # models.py:142-154 (output cast to f32)

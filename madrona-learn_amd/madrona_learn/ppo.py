@@ -141,8 +141,8 @@ class PPO(AlgoBase):  # ppo.py:49-106
         # surrogate and entropy are means over its own sub-actions, summed over
         # the keys, each entropy with its key's coefficient -> per sub-action
         # weights K / K_key (mlearn_ppo_hparams.obj_weight)
-        from .models import action_groups
-        groups = action_groups(cfg.actions)
+        from .models import _discrete_only, action_groups
+        groups = _discrete_only(action_groups(cfg.actions), "the fused PPO update")
         if sum(len(b) for _, b in groups) != K or \
                 tuple(x for _, b in groups for x in b) != tuple(policy_state.arch.buckets):
             raise ValueError(f"TrainConfig.actions {groups} does not match the actor's head "

@@ -177,11 +177,15 @@ class RolloutData:  # rollouts.py:311-334
 
 
 class RolloutStore:
-    def __init__(self, T, N, obs_dim, K, compute_dtype, device, num_chunks=1, rnn_hidden=0):
+    def __init__(self, T, N, obs_dim, K, compute_dtype, device, num_chunks=1, rnn_hidden=0,
+                 action_dtype=torch.int32):
         self.T, self.N = T, N
         f32 = torch.float32
         self.obs = torch.zeros((T, N, obs_dim), dtype=compute_dtype, device=device)
-        self.actions = torch.zeros((T, N, K), dtype=torch.int32, device=device)
+        # K action columns: int32 bucket indices, or f32 for continuous actions
+        # (K = G D; the same element width, so StoreCols addresses are unchanged)
+        assert action_dtype in (torch.int32, torch.float32)
+        self.actions = torch.zeros((T, N, K), dtype=action_dtype, device=device)
         self.log_probs = torch.zeros((T, N, K), dtype=f32, device=device)
         self.values = torch.zeros((T, N), dtype=f32, device=device)
         self.rewards = torch.zeros((T, N), dtype=f32, device=device)
@@ -373,7 +377,17 @@ def prep_obs(policy_state, prefix, obs, N):
 def sim_actions(actions, groups):
     """The sim's 'actions' input: the [N, K] tensor itself, or with several
     action groups (models.action_groups) a dict keyed like TrainConfig.actions
-    of [N, K_g] views (rollouts.py:985-1002)."""
+    of [N, K_g] views (rollouts.py:985-1002).  Continuous groups (f32 [N, G D]
+    columns): [N, 1, D] for one group (rollouts.py:991-996), else a dict of
+    [N, 1, D] views."""
+    if getattr(groups[0], "kind", "discrete") == "continuous":
+        if len(groups) == 1:
+            return actions.reshape(actions.shape[0], 1, -1)
+        out, off = {}, 0
+        for g in groups:
+            out[g[0]] = actions[:, off:off + g.cols].unsqueeze(1)
+            off += g.cols
+        return out
     if len(groups) == 1:
         return actions
     out, off = {}, 0
@@ -488,8 +502,10 @@ class RolloutManager:  # rollouts.py:373-826
         arch = self.policy_state.arch
         for ps in self.policies[1:]:
             assert ps.arch == arch, "population policies must share one architecture"
-        self.store = RolloutStore(self.T, self.NT, arch.obs_dim, arch.num_groups, arch.dtype,
-                                  self.policy_state.device, self.C, arch.lstm_hidden)
+        self.store = RolloutStore(self.T, self.NT, arch.obs_dim,
+                                  getattr(arch, "action_cols", arch.num_groups), arch.dtype,
+                                  self.policy_state.device, self.C, arch.lstm_hidden,
+                                  action_dtype=getattr(arch, "action_dtype", torch.int32))
         # GAE without a value normaliser: returns not materialised (RolloutStore)
         self.store.derive_returns = bool(train_cfg.compute_advantages and
                                          not train_cfg.normalize_values)

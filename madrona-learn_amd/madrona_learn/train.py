@@ -553,8 +553,11 @@ def _fused_tree_problem(policy, rollout_state, sim_batch, cfg):
     compute dtype, a tree or preprocess it does not implement, the
     normaliser-before-prefix order); any other error -- e.g. an even
     DreamerV3Critic num_bins, or a bug inside a user's prefix -- propagates."""
+    from .models import action_groups, continuous_groups
     from .rollouts import obs_to_matrix
     ac = policy.actor_critic
+    if continuous_groups(action_groups(cfg.actions)) is not None:
+        return "continuous actions (the fused kernels have discrete heads only)"
     if cfg.compute_dtype == torch.float16:
         return "fp16 compute dtype (DynamicScale, ppo.py:276-291)"
     bb = getattr(ac, "backbone", None)
@@ -597,7 +600,7 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
     import copy
     import sys
     from .generic import TorchPolicyState, TorchPPO, TorchTrainState, _has_state
-    from .models import action_groups
+    from .models import action_groups, continuous_groups
     P = len(policy_ids)
     if num_policies > 1:
         if _has_state(policy.obs_preprocess):
@@ -608,7 +611,11 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
             raise NotImplementedError("a recurrent population on the torch path")
     print(f"[madrona_learn] policy tree outside the fused kernels ({why}): training it with "
           "torch autograd (HIP sampling / GAE / statistics / optimizer)", file=sys.stderr)
-    buckets = [b for _, g in action_groups(cfg.actions) for b in g]
+    groups = action_groups(cfg.actions)
+    # (continuous groups have no buckets: TorchPolicyState reads the head's
+    # [G, D] from the actor's output, TorchPPO.prepare checks it against cfg)
+    buckets = [] if continuous_groups(groups) is not None else \
+        [b for _, g in groups for b in g]
     pss, tss, algos = [], [], []
     # policy 0 keeps the user's modules (and cfg.seed: single-policy runs are
     # unchanged); the others train copies taken before any of them creates
