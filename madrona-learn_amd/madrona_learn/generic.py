@@ -45,7 +45,7 @@ with the rollout carry and per-chunk start states.  After one eager update
 the whole update (rollout included: the sampling kernel reads the device
 step counter itself) is captured in HIP graphs; where the user's sim or
 modules cannot be captured, the PPO update alone, else nothing
-(TrainingManager._update_torch; fp16 stays eager).
+(TrainingManager._graphed; fp16 stays eager).
 """
 
 import ctypes
@@ -63,9 +63,10 @@ from .dynamic_scale import DynamicScale
 from .models import LayerNorm, _Dense, action_groups, continuous_groups
 from .observations import ObservationsPreprocess, _wrap
 from .pbt import MovingEpisodeScore
-from .ppo import _base
+from .ppo import PPO, _base
 from .rnn import MultiLayerLSTMCell
 from .train_state import _ckpt_safe
+from .tree import leaf_pairs, leaves, map_leaves, zip_leaves
 
 
 @dataclass(frozen=True)
@@ -246,13 +247,13 @@ class TorchPolicyState:
         torch.manual_seed(int(seed))
         with torch.no_grad():
             one = _slice_obs(pre, 0, 1)
-            rnn = _to_device(self.actor_critic.init_recurrent_state(1), device)
+            rnn = map_leaves(lambda x: x.to(device), self.actor_critic.init_recurrent_state(1))
             # recurrent trees (e.g. a multi-layer rnn.LSTM) carry their state
             # through the rollout (rollout_state.rnn_states) and train from the
             # per-chunk start states (TorchRollout / TorchPPO); otherwise the
             # tree's (empty) state structure, e.g. ((), ()) for
             # BackboneSeparate, is passed wherever the tree takes rnn states
-            self.recurrent = rnn not in ((), None) and _nonempty(rnn)
+            self.recurrent = rnn not in ((), None) and any(x is not None for x in leaves(rnn))
             self.rnn0 = rnn
             out, _ = self.actor_critic.rollout(PhiloxKey(0, 0), rnn, one)
         crit = out["critic"]
@@ -328,7 +329,7 @@ class TorchPolicyState:
     def load_state_dict(self, sd):
         self.params.copy_(sd["params"])
         if sd.get("obs_pre_state") is not None:
-            st = _to_device(sd["obs_pre_state"], self.device)
+            st = map_leaves(lambda x: x.to(self.device), sd["obs_pre_state"])
             if self._bare_obs:
                 st = _wrap(st)
             self.obs_pre_state = st
@@ -337,80 +338,22 @@ class TorchPolicyState:
         return [self.params]
 
 
-def _to_device(x, dev):
-    if isinstance(x, torch.Tensor):
-        return x.to(dev)
-    if isinstance(x, dict):
-        r = {k: _to_device(v, dev) for k, v in x.items()}
-        return type(x)(r) if type(x) is not dict else r  # (keeps a _Bare marker)
-    if isinstance(x, (list, tuple)):
-        return type(x)(_to_device(v, dev) for v in x)
-    return x
-
-
-def _map_leaves(fn, x):
-    """fn over every tensor of a recurrent-state pytree (lists / tuples / dicts)."""
-    if isinstance(x, torch.Tensor):
-        return fn(x)
-    if isinstance(x, dict):
-        return {k: _map_leaves(fn, v) for k, v in x.items()}
-    if isinstance(x, (list, tuple)):
-        return type(x)(_map_leaves(fn, v) for v in x)
-    return x
-
-
-def _zip_leaves(fn, a, b):
-    """fn(a_leaf, b_leaf) over two pytrees of the same structure."""
-    if isinstance(a, torch.Tensor):
-        fn(a, b)
-    elif isinstance(a, dict):
-        for k in a:
-            _zip_leaves(fn, a[k], b[k])
-    elif isinstance(a, (list, tuple)):
-        for x, y in zip(a, b):
-            _zip_leaves(fn, x, y)
-
-
-def _leaf_pairs(a, b, out):
-    if isinstance(a, torch.Tensor):
-        out.append((a, b))
-        return isinstance(b, torch.Tensor)
-    if isinstance(a, dict):
-        return isinstance(b, dict) and a.keys() == b.keys() and \
-            all(_leaf_pairs(a[k], b[k], out) for k in a)
-    if isinstance(a, (list, tuple)):
-        return isinstance(b, (list, tuple)) and len(a) == len(b) and \
-            all(_leaf_pairs(x, y, out) for x, y in zip(a, b))
-    return a is b or (isinstance(a, (int, float, bool, str, type(None))) and type(a) is type(b)
-                      and a == b)
-
-
 def _carry_back(start, cur):
     """State carried from one update to the next (the sim state, the current
     observations, the recurrent carry, a preprocess's estimates) kept at the
     addresses it had when the update began: cur's tensors are copied into
     start's, which is returned.  A captured update (HIP graph) reads these
     tensors at its start and must find the previous replay's values there.
-    cur is returned as is where the structures, shapes or dtypes differ."""
-    pairs = []
-    if start is cur or not _leaf_pairs(start, cur, pairs):
-        return cur
-    if any(a.shape != b.shape or a.dtype != b.dtype or a.device != b.device for a, b in pairs):
+    cur is returned as is where the structures, shapes, dtypes or devices
+    differ or a non-tensor leaf changed."""
+    pairs = None if start is cur else leaf_pairs(start, cur)
+    if pairs is None or any(a.shape != b.shape or a.dtype != b.dtype or a.device != b.device
+                            for a, b in pairs):
         return cur
     for a, b in pairs:
         if a is not b:
             a.copy_(b)
     return start
-
-
-def _nonempty(x):
-    if isinstance(x, torch.Tensor):
-        return True
-    if isinstance(x, (tuple, list)):
-        return any(_nonempty(y) for y in x)
-    if isinstance(x, dict):
-        return any(_nonempty(y) for y in x.values())
-    return x is not None
 
 
 def _has_state(pre):
@@ -561,10 +504,11 @@ class TorchRollout:
             # the live carry in sim order (rollouts.py:898-901, 941-942) and
             # the carry entering every BPTT chunk (rnn_start_states,
             # rollouts.py:528-537), one [C][N][...] tensor per state leaf
-            rollout_state.rnn_states = _to_device(rollout_state.rnn_states, m.policy_state.device)
+            rollout_state.rnn_states = map_leaves(lambda x: x.to(m.policy_state.device),
+                                                  rollout_state.rnn_states)
             bptt, C = m.bptt, m.C
             if getattr(s, "torch_start", None) is None:
-                s.torch_start = _map_leaves(
+                s.torch_start = map_leaves(
                     lambda x: torch.zeros((C, *x.shape), dtype=x.dtype, device=x.device),
                     rollout_state.rnn_states)
             start_rnn = rollout_state.rnn_states
@@ -575,8 +519,8 @@ class TorchRollout:
                 if one:
                     ps.observe(t, obs)
                 if rec and t % bptt == 0:
-                    _zip_leaves(lambda dst, src: dst[t // bptt].copy_(src), s.torch_start,
-                                rollout_state.rnn_states)
+                    zip_leaves(lambda dst, src: dst[t // bptt].copy_(src), s.torch_start,
+                               rollout_state.rnn_states)
                 with torch.no_grad():
                     out, rnn_out = ps.actor_critic.rollout(
                         PhiloxKey(key[0], key[1], t, m.env_offset + p * B, ctr=ctr),
@@ -605,70 +549,25 @@ class TorchRollout:
             rollout_state.rnn_states = _carry_back(start_rnn, rollout_state.rnn_states)
 
 
-class TorchPPO:
+class TorchPPO(PPO):
     """_ppo (ppo.py:366-488) for a torch-path policy: the fused path's
     permutation and per-minibatch advantage statistics (HIP, all-reduced
     under DP), then per minibatch the loss of ppo.py:129-262 under torch
     autograd over ActorCritic.update, the gradient all-reduce, and the flat
     HIP optimizer step."""
 
-    def __init__(self, base):
-        self.base = base  # the fused PPO instance (its prepare() buffers are reused)
-
-    def __getattr__(self, k):
-        return getattr(self.base, k)
-
-    def add_metrics(self, cfg, names):
-        return self.base.add_metrics(cfg, names)
-
-    def init_hyperparams(self, cfg):
-        return self.base.init_hyperparams(cfg)
-
-    def prepare(self, cfg, ps, ts, view, dp, policy_idx=0, start_states=None):
-        b = self.base
+    def prepare(self, cfg, ps, ts, view, dp, store, col0=0, policy_idx=0):
+        """``store``: the RolloutManager's store; ``col0``: this policy's first
+        env column in it (a population's policy p: col0 = p B)."""
         algo = cfg.algo
-        if cfg.filter_advantages or cfg.importance_sample_trajectories:
-            raise NotImplementedError("filter_advantages / importance_sample_trajectories")
-        C = cfg.num_bptt_chunks
-        b.bptt = cfg.steps_per_update // C
-        b.num_seq = C * view.N
-        G = dp.world_size
-        if int(algo.minibatch_size) % G != 0:
-            raise ValueError(f"minibatch_size {algo.minibatch_size} does not split over {G} ranks")
-        b.mb = int(algo.minibatch_size) // G
-        if b.num_seq % b.mb != 0:  # ppo.py:439
-            raise ValueError(f"{b.num_seq * G} sequences not divisible by minibatch_size "
-                             f"{algo.minibatch_size}")
-        b.num_mb = b.num_seq // b.mb
-        b.E = int(algo.num_epochs)
-        dev = ps.device
-        b.perm = torch.zeros((b.E, b.num_seq), dtype=torch.int32, device=dev)
-        b.adv_part = torch.zeros((b.E, b.num_mb * 66), dtype=torch.float64, device=dev)
-        b.adv_stats = torch.zeros((b.E, b.num_mb, 2), dtype=torch.float32, device=dev)
-        b.adv_sums = torch.zeros((b.E, 2 * b.num_mb), dtype=torch.float64, device=dev)
-        b.view = view
-        b.policy_idx = policy_idx
-        b.dp = dp
-        b.count = float(b.mb * dp.world_size * b.bptt)
-        # value normaliser (normalize_values, ppo.py:190-211): the same
-        # per-minibatch return sums and estimate chain as the fused path
-        # (mlearn_return_stats / mlearn_value_norm_chain); the loss reads
-        # record m = {adv mean, adv rstd, mu', inv_sigma' after minibatch m's
-        # update, mu, sigma before it}
-        b.vnorm = bool(cfg.normalize_values)
-        if b.vnorm and ps.critic_bins > 1:
+        self._plan_minibatches(cfg, view, dp, ps.device, ts, policy_idx)
+        self.store, self.col0 = store, int(col0)
+        if self.vnorm and ps.critic_bins > 1:
             # ppo.py:57 asserts not normalize_values for distributional
             # critics: the two-hot loss ignores the normaliser, yet GAE would
             # invert the two-hot mean with drifting estimates
             raise ValueError("normalize_values with a SymExpTwoHotDistribution / HLGaussDist "
                              "critic (the reference asserts against it, ppo.py:57)")
-        if b.vnorm:
-            b.vn_est = ts.value_norm_est
-            b.vn_count = ts.value_norm_count
-            b.vn_decay = float(cfg.value_normalizer_decay)
-            b.ret_part = torch.zeros_like(b.adv_part)
-            b.vn_rec = torch.zeros((b.E, b.num_mb, 8), dtype=torch.float32, device=dev)
-            b.adv_sums = torch.zeros((b.E, 4 * b.num_mb), dtype=torch.float64, device=dev)
         self.groups = action_groups(cfg.actions)
         self.cont = continuous_groups(self.groups)
         if self.cont is not None:
@@ -694,7 +593,10 @@ class TorchPPO:
         self.norm_adv = bool(cfg.normalize_advantages if cfg.compute_advantages
                              else cfg.normalize_returns)
         self.loss_scale = 1.0 / dp.world_size
-        self.store = None  # set by init_training (the RolloutManager's store)
+
+    def _all_reduce_stats(self, sums):
+        # the one intended difference from the fused path: never the native communicator
+        yield ("allreduce", sums)
 
     def _minibatch(self, seqs):
         """RolloutData.minibatch (rollouts.py:319-329): whole sequences of
@@ -702,9 +604,7 @@ class TorchPPO:
         (c * bptt + t) * N + b with c, b = divmod(seq, N)."""
         s = self.store
         # this policy's env columns [col0, col0 + view.N) of the [T][N] store
-        # (a population's policy p: col0 = p B)
-        N, bp = int(self.view.N), self.bptt
-        col0 = int(getattr(self, "col0", 0))
+        N, bp, col0 = int(self.view.N), self.bptt, self.col0
         seq = seqs.long()
         c, b = seq // N, seq % N
         t = torch.arange(bp, device=seq.device)[:, None]
@@ -720,7 +620,7 @@ class TorchPPO:
                "dones": flat(s.dones)[rows]}
         if getattr(s, "torch_start", None) is not None:
             # rnn_start_states of the minibatch's sequences (chunk c, env b)
-            out["rnn_start"] = _map_leaves(lambda x: x[c, b], s.torch_start)
+            out["rnn_start"] = map_leaves(lambda x: x[c, b], s.torch_start)
         return out
 
     def _loss(self, ps, mbd, adv_stats):
@@ -778,7 +678,7 @@ class TorchPPO:
             V = crit.float().reshape(T, M)
             vpred = V
             tgt = R
-            if self.base.vnorm:
+            if self.vnorm:
                 # ppo.py:190-211: errors of the critic inverted with the estimates
                 # before this minibatch; the target = the returns normalised with
                 # the estimates after normalize_and_update_estimates
@@ -805,58 +705,28 @@ class TorchPPO:
 
     def update_program(self, cfg, policy_state, train_state, rollout_data, user_metrics_cb,
                        metrics, epoch_ctr):
-        b = self.base
-        L = nat.lib()
-        strm = nat.stream_handle()
-        k0, k1 = train_state.update_prng_key
-        for e in range(b.E):
-            nat.check(L.mlearn_minibatch_perm(k0, k1, nat.ptr(epoch_ctr), e, b.dp.rank,
-                                              b.num_seq, nat.ptr(b.perm[e]), strm), "perm")
-            nat.check(L.mlearn_adv_stats(b.view, nat.ptr(b.perm[e]), b.num_mb, b.mb,
-                                         nat.ptr(b.adv_part[e]), strm), "adv_stats")
-            if b.vnorm:
-                nat.check(L.mlearn_return_stats(b.view, nat.ptr(b.perm[e]), b.num_mb, b.mb,
-                                                nat.ptr(b.ret_part[e]), strm), "return_stats")
-        n2 = 2 * b.num_mb
-        if b.dp.world_size > 1:
-            for e in range(b.E):
-                b.adv_sums[e, :n2].copy_(b.adv_part[e, :n2])
-                if b.vnorm:
-                    b.adv_sums[e, n2:2 * n2].copy_(b.ret_part[e, :n2])
-            yield ("allreduce", b.adv_sums)
-            for e in range(b.E):
-                b.adv_part[e, :n2].copy_(b.adv_sums[e, :n2])
-                if b.vnorm:
-                    b.ret_part[e, :n2].copy_(b.adv_sums[e, n2:2 * n2])
-        for e in range(b.E):
-            nat.check(L.mlearn_adv_stats_finish(nat.ptr(b.adv_part[e]), b.num_mb, b.count,
-                                                nat.ptr(b.adv_stats[e]), strm), "adv_stats_finish")
-        if b.vnorm:  # the estimates move minibatch by minibatch, epochs in order (ppo.py:346)
-            for e in range(b.E):
-                nat.check(L.mlearn_value_norm_chain(
-                    nat.ptr(b.ret_part[e]), nat.ptr(b.adv_stats[e]), b.num_mb, b.count,
-                    b.vn_decay, 1e-5, nat.ptr(b.vn_est), nat.ptr(b.vn_count),
-                    nat.ptr(b.vn_rec[e]), strm), "value_norm_chain")
+        yield from self._minibatch_stats_program(train_state, epoch_ctr)
         ps, ts = policy_state, train_state
-        for e in range(b.E):
-            for m in range(b.num_mb):
-                seqs = b.perm[e, m * b.mb:(m + 1) * b.mb]
+        for e in range(self.E):
+            for m in range(self.num_mb):
+                seqs = self.perm[e, m * self.mb:(m + 1) * self.mb]
                 mbd = self._minibatch(seqs)
                 ps.grads.zero_()
-                loss, met = self._loss(ps, mbd, b.vn_rec[e, m] if b.vnorm else b.adv_stats[e, m])
+                stats = self.vn_rec[e, m] if self.vnorm else self.adv_stats[e, m]
+                loss, met = self._loss(ps, mbd, stats)
                 sc = ts.scaler
                 if sc is None:
                     (loss * self.loss_scale).backward()
                 else:  # DynamicScale.value_and_grad: scaled loss, f32 gradient / scale
                     sc.scale_loss(loss * self.loss_scale).backward()
                     sc.unscale_(ps.grads)
-                if b.dp.world_size > 1:
+                if self.dp.world_size > 1:
                     yield ("allreduce", ps.grads)
                 ts.optimizer_step(ps)
                 if sc is not None:
                     sc.update(ps.grads)
-                if e == b.E - 1 and m == b.num_mb - 1:
-                    _record_metrics(metrics, b.policy_idx, met)
+                if e == self.E - 1 and m == self.num_mb - 1:
+                    _record_metrics(metrics, self.policy_idx, met)
                 metrics = user_metrics_cb(metrics, e, {"sequence_ids": seqs}, ps, ts)
         return metrics
 

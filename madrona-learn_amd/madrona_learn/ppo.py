@@ -84,12 +84,9 @@ class PPO(AlgoBase):  # ppo.py:49-106
         return list(names) + PPO_METRICS
 
     # ------------------------------------------------------------------
-    def prepare(self, cfg, policy_state, train_state, view, dp, policy_idx=0, start_states=None):
-        """Allocate the per-update buffers once (graph-capture safe).  ``view``
-        is the rollout view of this policy's env columns; ``dp`` the data
-        parallel group that trains this policy; ``policy_idx`` its slot in the
-        rank's metrics; ``start_states`` the device pointers of this policy's
-        rnn_start_states (recurrent policies)."""
+    def _plan_minibatches(self, cfg, view, dp, device, train_state, policy_idx):
+        """The minibatch plan and the per-update statistics buffers both update
+        paths share (allocated once: graph-capture safe)."""
         algo = cfg.algo
         if cfg.filter_advantages or cfg.importance_sample_trajectories:
             raise NotImplementedError(
@@ -111,11 +108,40 @@ class PPO(AlgoBase):  # ppo.py:49-106
                              f"{algo.minibatch_size}")
         self.num_mb = self.num_seq // self.mb
         self.E = int(algo.num_epochs)
+        self.perm = torch.zeros((self.E, self.num_seq), dtype=torch.int32, device=device)
+        self.adv_part = torch.zeros((self.E, self.num_mb * 66), dtype=torch.float64,
+                                    device=device)
+        self.adv_stats = torch.zeros((self.E, self.num_mb, 2), dtype=torch.float32, device=device)
+        self.adv_sums = torch.zeros((self.E, 2 * self.num_mb), dtype=torch.float64, device=device)
+        self.view = view
+        self.policy_idx = policy_idx
+        self.dp = dp
+        self.count = float(self.mb * dp.world_size * self.bptt)
+        # value normaliser (normalize_values, ppo.py:190-211): the returns'
+        # per-minibatch sums join the advantage sums' collective; one chain
+        # launch per epoch turns them into per-minibatch records {adv mean,
+        # adv rstd, mu', inv_sigma' after minibatch m's update, mu, sigma
+        # before it}
+        self.vnorm = bool(cfg.normalize_values)
+        if self.vnorm:
+            self.vn_est = train_state.value_norm_est
+            self.vn_count = train_state.value_norm_count
+            self.vn_decay = float(cfg.value_normalizer_decay)
+            self.ret_part = torch.zeros_like(self.adv_part)
+            self.vn_rec = torch.zeros((self.E, self.num_mb, 8), dtype=torch.float32,
+                                      device=device)
+            self.adv_sums = torch.zeros((self.E, 4 * self.num_mb), dtype=torch.float64,
+                                        device=device)
+
+    def prepare(self, cfg, policy_state, train_state, view, dp, policy_idx=0, start_states=None):
+        """Allocate the per-update buffers once (graph-capture safe).  ``view``
+        is the rollout view of this policy's env columns; ``dp`` the data
+        parallel group that trains this policy; ``policy_idx`` its slot in the
+        rank's metrics; ``start_states`` the device pointers of this policy's
+        rnn_start_states (recurrent policies)."""
+        algo = cfg.algo
         dev = policy_state.device
-        self.perm = torch.zeros((self.E, self.num_seq), dtype=torch.int32, device=dev)
-        self.adv_part = torch.zeros((self.E, self.num_mb * 66), dtype=torch.float64, device=dev)
-        self.adv_stats = torch.zeros((self.E, self.num_mb, 2), dtype=torch.float32, device=dev)
-        self.adv_sums = torch.zeros((self.E, 2 * self.num_mb), dtype=torch.float64, device=dev)
+        self._plan_minibatches(cfg, view, dp, dev, train_state, policy_idx)
         rows = self.mb * self.bptt
         self.lstm = policy_state.lstm_desc
         if self.lstm is not None:
@@ -131,8 +157,6 @@ class PPO(AlgoBase):  # ppo.py:49-106
         else:
             nbytes = nat.lib().mlearn_ppo_workspace_bytes(policy_state.desc, rows)
         self.ws = torch.zeros(int(nbytes), dtype=torch.uint8, device=dev)
-        self.view = view
-        self.policy_idx = policy_idx
         K = policy_state.arch.num_groups
         hp = nat.PPOHparams()
         hp.clip_coef = float(algo.clip_coef)
@@ -183,28 +207,23 @@ class PPO(AlgoBase):  # ppo.py:49-106
             hp.grad_sumsq_out = self.gsq.data_ptr()
             train_state.optim_desc.grad_sumsq_part = self.gsq.data_ptr()
             train_state.optim_desc.grad_sumsq_nparts = nparts
-        # value normaliser (normalize_values, ppo.py:190-211): the returns'
-        # per-minibatch sums join the advantage sums' collective; one chain
-        # launch per epoch turns them into per-minibatch estimate records
-        self.vnorm = bool(cfg.normalize_values)
         hp.normalize_values = 1 if self.vnorm else 0
-        if self.vnorm:
-            self.vn_est = train_state.value_norm_est
-            self.vn_count = train_state.value_norm_count
-            self.vn_decay = float(cfg.value_normalizer_decay)
-            self.ret_part = torch.zeros_like(self.adv_part)
-            self.vn_rec = torch.zeros((self.E, self.num_mb, 8), dtype=torch.float32, device=dev)
-            self.adv_sums = torch.zeros((self.E, 4 * self.num_mb), dtype=torch.float64, device=dev)
         self.hp = hp
-        self.dp = dp
-        self.count = float(self.mb * dp.world_size * self.bptt)
 
-    def update_program(self, cfg, policy_state, train_state, rollout_data, user_metrics_cb,
-                       metrics, epoch_ctr):
+    def _all_reduce_stats(self, sums):
+        # the one intended difference between the update paths: TorchPPO always yields
+        if self.dp.comm is not None:
+            self.dp.native_all_reduce_sum_(sums)
+        else:
+            yield ("allreduce", sums)
+
+    def _minibatch_stats_program(self, train_state, epoch_ctr):
+        """The update's prologue on both paths: every epoch's permutation,
+        the per-minibatch advantage (and return) statistics, all-reduced under
+        DP, and the value normaliser's per-minibatch records."""
         L = nat.lib()
         strm = nat.stream_handle()
         k0, k1 = train_state.update_prng_key
-        # epoch permutations + advantage statistics for every minibatch of the update
         for e in range(self.E):
             nat.check(L.mlearn_minibatch_perm(k0, k1, nat.ptr(epoch_ctr), e, self.dp.rank,
                                               self.num_seq, nat.ptr(self.perm[e]), strm), "perm")
@@ -221,10 +240,7 @@ class PPO(AlgoBase):  # ppo.py:49-106
                 self.adv_sums[e, :n2].copy_(self.adv_part[e, :n2])
                 if self.vnorm:
                     self.adv_sums[e, n2:].copy_(self.ret_part[e, :n2])
-            if self.dp.comm is not None:
-                self.dp.native_all_reduce_sum_(self.adv_sums)
-            else:
-                yield ("allreduce", self.adv_sums)
+            yield from self._all_reduce_stats(self.adv_sums)
             for e in range(self.E):
                 self.adv_part[e, :n2].copy_(self.adv_sums[e, :n2])
                 if self.vnorm:
@@ -240,6 +256,12 @@ class PPO(AlgoBase):  # ppo.py:49-106
                     nat.ptr(self.ret_part[e]), nat.ptr(self.adv_stats[e]), self.num_mb,
                     self.count, self.vn_decay, 1e-5, nat.ptr(self.vn_est), nat.ptr(self.vn_count),
                     nat.ptr(self.vn_rec[e]), strm), "value_norm_chain")
+
+    def update_program(self, cfg, policy_state, train_state, rollout_data, user_metrics_cb,
+                       metrics, epoch_ctr):
+        L = nat.lib()
+        strm = nat.stream_handle()
+        yield from self._minibatch_stats_program(train_state, epoch_ctr)
         loss_out = metrics.slots("Loss", 5, policy=self.policy_idx)
         for e in range(self.E):
             for m in range(self.num_mb):

@@ -11,6 +11,7 @@ data-parallel collectives (if any) issued between graph segments.
 
 import os
 import re
+import sys
 from dataclasses import dataclass
 from typing import Any, Callable, Dict, Optional
 
@@ -25,6 +26,7 @@ from .policy import Policy
 from .profile import profile
 from .rollouts import RolloutConfig, RolloutManager, RolloutState
 from .train_state import PolicyState, PolicyTrainState, TrainStateManager, compile_arch
+from .tree import leaves, map_leaves, zip_leaves
 
 
 @dataclass(frozen=True)
@@ -58,7 +60,8 @@ def _split_seed(seed, stream):
 
 class TrainingManager:  # train.py:35-64
     def __init__(self, state, rollout, metrics, cfg, rollout_mgr, algos, user_hooks, dp,
-                 update_idx=0, use_graph=True, profile_port=None):
+                 update_idx=0, use_graph=True, profile_port=None, torch_path=False,
+                 sim_get_ckpts=None, sim_load_ckpts=None):
         self.state = state
         self.rollout = rollout
         self.metrics = metrics
@@ -73,15 +76,16 @@ class TrainingManager:  # train.py:35-64
         self.profile_port = profile_port
         self._segments = None
         self._eager_iters = 0
-        # "all": the whole update is captured (the fused kernels); "learn":
-        # the torch path (generic.py) -- its rollout runs eagerly (it reads the
-        # device sampling counter on the host once per rollout) and the PPO
-        # update (autograd through the user's modules, HIP action_stats and
-        # flat optimizer) is captured; a tree whose modules cannot be captured
-        # falls back to eager updates
+        # what use_graph captures.  "all": the whole update, rollout included
+        # (the fused kernels, and the torch path of generic.py, whose sampling
+        # kernel reads the device step counter itself); "learn": the PPO update
+        # only, after an eager rollout -- where the torch path falls to when
+        # the user's sim or modules cannot be captured (_rollout_not_capturable)
         self.graph_scope = "all"
         self._side = None  # the torch path's stream (its warm-up and capture)
-        self._torch_path = False  # set by _init_training_torch (see _update_torch)
+        self._torch_path = torch_path  # generic.py's policies (see update_iter)
+        self._sim_get_ckpts = sim_get_ckpts  # sim_fns' 'get_ckpts' / 'load_ckpts'
+        self._sim_load_ckpts = sim_load_ckpts
 
     # -- one update as a generator over collectives --------------------------
     def _collect(self):
@@ -106,8 +110,7 @@ class TrainingManager:  # train.py:35-64
             self._collect()
             yield from self._learn()
 
-    def _run_eager(self, gen=None):
-        gen = self._program() if gen is None else gen
+    def _run_eager(self, gen):
         try:
             while True:
                 op, t = next(gen)
@@ -116,13 +119,11 @@ class TrainingManager:  # train.py:35-64
         except StopIteration:
             pass
 
-    def _capture(self, gen=None, s=None):
-        """Capture the update (or the generator gen) into HIP graphs split at
-        the collectives."""
-        gen = self._program() if gen is None else gen
+    def _capture(self, gen, s):
+        """Capture the generator gen (an update, or its PPO part) on stream s
+        into HIP graphs split at the collectives."""
         segments = []
         done = False
-        s = torch.cuda.Stream() if s is None else s
         s.wait_stream(torch.cuda.current_stream())
         while not done:
             g = torch.cuda.CUDAGraph()
@@ -143,38 +144,6 @@ class TrainingManager:  # train.py:35-64
             if coll is not None:
                 self.dp.all_reduce_sum_(coll)
 
-    def _update_learn_graph(self):
-        """graph_scope "learn": eager rollout, then the update from HIP graphs
-        (one eager update first, on the stream the capture uses, so that the
-        lazily created library handles and autograd's stream state exist
-        before capture)."""
-        import sys
-        self._collect()
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-        cur = torch.cuda.current_stream()
-        if self._segments is None and self._eager_iters >= 1:
-            try:
-                self._segments = self._capture(self._learn(), self._side)
-            except RuntimeError as e:  # modules with host reads / syncs: stay eager
-                cur.wait_stream(self._side)
-                torch.cuda.synchronize()
-                print(f"[madrona_learn] torch-path update not capturable ({type(e).__name__}: "
-                      f"{e}); updating eagerly", file=sys.stderr)
-                self._segments = None
-                self.use_graph = False
-                self._run_eager(self._learn())
-                return
-            self._replay()  # the capture recorded the update without running it
-        elif self._segments is not None:
-            self._replay()
-        else:
-            self._side.wait_stream(cur)
-            with torch.cuda.stream(self._side):
-                self._run_eager(self._learn())
-            cur.wait_stream(self._side)
-            self._eager_iters += 1
-
     def _host_refs(self):
         # the Python references a (failed) capture may have moved to tensors
         # of its never-executed graph (sim state, observations, carries, ...)
@@ -182,70 +151,77 @@ class TrainingManager:  # train.py:35-64
         objs += list(self.state.policy_list) + list(self.state.train_list)
         return [(o, dict(vars(o))) for o in objs]
 
-    @staticmethod
-    def _restore_host_refs(saved):
-        for o, d in saved:
+    def _graphed(self, program, on_fail=None):
+        """One run of ``program`` (_program or _learn) under use_graph: the
+        first runs eagerly (so that the lazily created library handles and
+        autograd's stream state exist before capture), the second captures it
+        into HIP graphs split at the collectives, and it replays from then on.
+        The fused path (on_fail None) warms up on the current stream and
+        captures on a fresh one; the torch path does both on its side stream
+        and, when the capture raises, calls on_fail(error, host references
+        saved before the capture)."""
+        if self._segments is not None:
+            return self._replay()
+        cur = torch.cuda.current_stream()
+        if on_fail is not None and self._side is None:
+            self._side = torch.cuda.Stream()
+        if self._eager_iters < 1:
+            if on_fail is None:
+                self._run_eager(program())
+            else:
+                self._side.wait_stream(cur)
+                with torch.cuda.stream(self._side):
+                    self._run_eager(program())
+                cur.wait_stream(self._side)
+            self._eager_iters += 1
+            return
+        side, saved = (torch.cuda.Stream(), None) if on_fail is None else \
+            (self._side, self._host_refs())
+        try:
+            self._segments = self._capture(program(), side)
+        except RuntimeError as e:
+            if on_fail is None:
+                raise
+            cur.wait_stream(side)
+            torch.cuda.synchronize()
+            return on_fail(e, saved)
+        self._replay()  # the capture recorded the update without running it
+
+    def _rollout_not_capturable(self, e, saved):
+        """The user's sim or modules cannot be captured: capture the PPO
+        update only from now on (graph_scope "learn")."""
+        for o, d in saved:  # (the failed capture moved them)
             vars(o).clear()
             vars(o).update(d)
+        print(f"[madrona_learn] torch-path rollout not capturable ({type(e).__name__}: "
+              f"{e}); capturing the PPO update only", file=sys.stderr)
+        self.graph_scope = "learn"
+        self._collect()
+        self._graphed(self._learn, self._update_not_capturable)
 
-    def _update_torch(self):
-        """The torch path (generic.py) under use_graph: update 1 runs eagerly
-        on the capture stream; update 2 captures the whole program (rollout +
-        update, split at the collectives) and replays it from then on.  If the
-        user's sim or modules cannot be captured, the host references the
-        failed capture moved are restored and only the PPO update is captured
-        (graph_scope "learn"; if that fails too, updates run eagerly)."""
-        import sys
-        if self.graph_scope == "learn":
-            return self._update_learn_graph()
-        if self._side is None:
-            self._side = torch.cuda.Stream()
-        cur = torch.cuda.current_stream()
-        if self._segments is not None:
-            self._replay()
-        elif self._eager_iters < 1:
-            self._side.wait_stream(cur)
-            with torch.cuda.stream(self._side):
-                self._run_eager()
-            cur.wait_stream(self._side)
-            self._eager_iters += 1
-        else:
-            saved = self._host_refs()
-            try:
-                self._segments = self._capture(self._program(), self._side)
-            except RuntimeError as e:
-                cur.wait_stream(self._side)
-                torch.cuda.synchronize()
-                self._restore_host_refs(saved)
-                print(f"[madrona_learn] torch-path rollout not capturable ({type(e).__name__}: "
-                      f"{e}); capturing the PPO update only", file=sys.stderr)
-                self.graph_scope = "learn"
-                return self._update_learn_graph()
-            self._replay()  # the capture recorded the update without running it
+    def _update_not_capturable(self, e, saved):
+        """Modules with host reads / syncs: stay eager."""
+        print(f"[madrona_learn] torch-path update not capturable ({type(e).__name__}: "
+              f"{e}); updating eagerly", file=sys.stderr)
+        self._segments = None
+        self.use_graph = False
+        self._run_eager(self._learn())
 
     def update_iter(self):
         """One PPO iteration; returns self (the reference returns a new pytree)."""
-        if self.use_graph and self._torch_path:
-            self._update_torch()
-        elif self.use_graph and self.graph_scope == "learn":
-            self._update_learn_graph()
-        elif self.use_graph and self._segments is None and self._eager_iters >= 1:
-            # capture runs the program once: it performs this iteration's work
-            self._segments = self._capture()
-            self._replay_collectives_of_capture()
-        elif self._segments is not None:
-            self._replay()
-        else:
-            self._run_eager()
+        if not self.use_graph:
+            self._run_eager(self._program())
             self._eager_iters += 1
+        elif not self._torch_path:
+            self._graphed(self._program)
+        elif self.graph_scope == "all":
+            self._graphed(self._program, self._rollout_not_capturable)
+        else:
+            self._collect()
+            self._graphed(self._learn, self._update_not_capturable)
         self.metrics.advance()
         self.update_idx += 1
         return self
-
-    def _replay_collectives_of_capture(self):
-        # Capturing records kernels without executing them: run the captured
-        # graphs once now so this call still performs exactly one update.
-        self._replay()
 
     def save_ckpt(self, path):  # train.py:44-46
         """<path>/<update_idx>.pt: the train state (TrainStateManager.save) plus
@@ -283,9 +259,8 @@ class TrainingManager:  # train.py:35-64
         if r.matchmake_key is not None:
             # the live matchmaking assignments (their step counter is counters[0])
             out["policy_assignments"] = r.policy_assignments.cpu()
-        get = getattr(self, "_sim_get_ckpts", None)
-        if get is not None:
-            out["sim"] = _to_cpu(get())
+        if self._sim_get_ckpts is not None:
+            out["sim"] = _to_cpu(self._sim_get_ckpts())
         return out
 
     def _load_rollout_state(self, sd):
@@ -296,9 +271,8 @@ class TrainingManager:  # train.py:35-64
         _copy_into(r.rnn_states, sd["rnn_states"])
         if r.matchmake_key is not None and sd.get("policy_assignments") is not None:
             r.policy_assignments.copy_(sd["policy_assignments"])
-        load = getattr(self, "_sim_load_ckpts", None)
-        if load is not None and sd.get("sim") is not None:
-            load(sd["sim"])
+        if self._sim_load_ckpts is not None and sd.get("sim") is not None:
+            self._sim_load_ckpts(sd["sim"])
 
 
 def _ckpt_name(update_idx, rank=0, world_size=1):
@@ -320,25 +294,16 @@ def _ckpt_file(path, rank=0, world_size=1):
 
 
 def _to_cpu(x):
-    if isinstance(x, torch.Tensor):
-        return x.detach().cpu()
-    if isinstance(x, dict):
-        return {k: _to_cpu(v) for k, v in x.items()}
-    if isinstance(x, (list, tuple)):
-        return [_to_cpu(v) for v in x]
-    return x
+    """The saved form of a tree: plain dicts, and tuples as lists (what every
+    checkpoint so far holds; _copy_into takes them back into tuples)."""
+    return map_leaves(lambda t: t.detach().cpu(), x,
+                      like=lambda c, vals: dict(zip(c, vals)) if isinstance(c, dict) else vals)
 
 
 def _copy_into(dst, src):
-    """Copy a saved tree into the live device tensors (same structure)."""
-    if isinstance(dst, torch.Tensor):
-        dst.copy_(src)
-    elif isinstance(dst, dict):
-        for k in dst:
-            _copy_into(dst[k], src[k])
-    elif isinstance(dst, (list, tuple)):
-        for d, s_ in zip(dst, src):
-            _copy_into(d, s_)
+    """Copy a saved tree into the live device tensors (dst's structure; a
+    saved list stands for a tuple, zip_leaves does not check src)."""
+    zip_leaves(lambda d, s_: d.copy_(s_), dst, src)
 
 
 def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: Policy,
@@ -498,9 +463,9 @@ def init_training(dev, cfg: TrainConfig, sim_fns: Dict[str, Callable], policy: P
                      start_states=rollout_mgr.start_states(p) if ps.recurrent else None)
     print(cfg)
     mgr = TrainingManager(tsm, rollout_state, metrics, cfg, rollout_mgr, algos, user_hooks, dp,
-                          update_idx=start, use_graph=use_graph, profile_port=profile_port)
-    mgr._sim_get_ckpts = sim_fns.get("get_ckpts")
-    mgr._sim_load_ckpts = sim_fns.get("load_ckpts")
+                          update_idx=start, use_graph=use_graph, profile_port=profile_port,
+                          sim_get_ckpts=sim_fns.get("get_ckpts"),
+                          sim_load_ckpts=sim_fns.get("load_ckpts"))
     return mgr
 
 
@@ -511,7 +476,7 @@ def _matchmaking_problem(cfg, policy, rnn_states, W):
     pbt = cfg.pbt
     if W > 1:
         return f"single rank only (this job has {W} ranks)"
-    if any(True for _ in _leaves(rnn_states)):
+    if _has_tensor(rnn_states):
         return "recurrent policies are not supported (no carry per assignment)"
     if isinstance(policy.obs_preprocess, ObservationsEMANormalizer):
         return ("an ObservationsEMANormalizer is not supported (the gathered step has no "
@@ -590,7 +555,7 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
                          policy_ids=(0,), use_graph=True):
     """init_training for a tree outside the fused kernels (generic.py): the
     user's torch modules train under autograd (captured in HIP graphs after
-    one eager update, TrainingManager._update_torch), with
+    one eager update, TrainingManager._graphed), with
     sampling, post-step, GAE, advantage statistics, action_stats and the
     optimizer on the HIP kernels.  A population (cfg.pbt, self-play split)
     gets one copy of the tree per train policy this rank holds, each with its
@@ -598,7 +563,6 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
     train_state.py:439-488; the reference vmaps algo.update over the policy
     axis, train.py:165-174), trained one after the other."""
     import copy
-    import sys
     from .generic import TorchPolicyState, TorchPPO, TorchTrainState, _has_state
     from .models import action_groups, continuous_groups
     P = len(policy_ids)
@@ -607,7 +571,7 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
             raise NotImplementedError(
                 "a population on the torch path with a stateful ObservationsPreprocess (its "
                 "per-policy state is not part of the PBT policy copies here)")
-        if any(True for _ in _leaves(policy.actor_critic.init_recurrent_state(1))):
+        if _has_tensor(policy.actor_critic.init_recurrent_state(1)):
             raise NotImplementedError("a recurrent population on the torch path")
     print(f"[madrona_learn] policy tree outside the fused kernels ({why}): training it with "
           "torch autograd (HIP sampling / GAE / statistics / optimizer)", file=sys.stderr)
@@ -631,7 +595,7 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
                               buckets, seed)
         _check_critic_flags(cfg, getattr(ac, "critic", None), ps.critic_form)
         dp.broadcast_(ps.params)
-        algo = TorchPPO(cfg.algo.setup())
+        algo = TorchPPO()
         ts = TorchTrainState(cfg, algo.init_hyperparams(cfg), ps,
                              _split_seed(cfg.seed, 2 + 16 * pid))
         ts.policy_id = pid
@@ -673,32 +637,22 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
     names = user_hooks.add_metrics(names)
     metrics = TrainingMetrics(names, cfg.metrics_buffer_size, device, num_policies=P)
     for i, (ps, ts, algo) in enumerate(zip(pss, tss, algos)):
-        algo.prepare(cfg, ps, ts, rollout_mgr.view(i), dp, policy_idx=i)
-        algo.store = rollout_mgr.store
-        algo.col0 = i * rollout_mgr.B
+        algo.prepare(cfg, ps, ts, rollout_mgr.view(i), dp, rollout_mgr.store,
+                     col0=i * rollout_mgr.B, policy_idx=i)
     print(cfg)
-    # HIP graphs (TrainingManager._update_torch: the whole update, else the
-    # PPO update only); fp16 (DynamicScale reads the gradient norm on the
-    # host) stays eager
-    mgr = TrainingManager(tsm, rollout_state, metrics, cfg, rollout_mgr, algos, user_hooks, dp,
-                          update_idx=start,
-                          use_graph=use_graph and all(ts.scaler is None for ts in tss),
-                          profile_port=profile_port)
-    mgr._torch_path = True  # whole-update capture, falling back to the update only
-    mgr._sim_get_ckpts = sim_fns.get("get_ckpts")
-    mgr._sim_load_ckpts = sim_fns.get("load_ckpts")
-    return mgr
+    # HIP graphs (TrainingManager.update_iter: the whole update, else the PPO
+    # update only); fp16 (DynamicScale reads the gradient norm on the host)
+    # stays eager
+    return TrainingManager(tsm, rollout_state, metrics, cfg, rollout_mgr, algos, user_hooks, dp,
+                           update_idx=start,
+                           use_graph=use_graph and all(ts.scaler is None for ts in tss),
+                           profile_port=profile_port, torch_path=True,
+                           sim_get_ckpts=sim_fns.get("get_ckpts"),
+                           sim_load_ckpts=sim_fns.get("load_ckpts"))
 
 
-def _leaves(x):
-    if isinstance(x, torch.Tensor):
-        yield x
-    elif isinstance(x, dict):
-        for v in x.values():
-            yield from _leaves(v)
-    elif isinstance(x, (list, tuple)):
-        for v in x:
-            yield from _leaves(v)
+def _has_tensor(x):
+    return any(isinstance(v, torch.Tensor) for v in leaves(x))
 
 
 def _obs_cols(obs, P, i):

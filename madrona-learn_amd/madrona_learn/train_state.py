@@ -25,6 +25,7 @@ from .models import (MLP, DenseLayerCritic, DenseLayerDiscreteActor, DreamerV3Cr
                      HLGaussCritic)
 from .observations import ObservationsEMANormalizer, ObservationsPreprocessNoop
 from .rnn import LSTM
+from .tree import map_leaves
 
 
 @dataclass(frozen=True)
@@ -708,11 +709,9 @@ class TrainStateManager:  # train_state.py:139-304
 def _ckpt_safe(x):
     """user_state as saved: tensors / numbers / strings and dicts, lists or
     tuples of them (what a weights_only load restores); anything else is not
-    checkpointed."""
-    if x is None or isinstance(x, (torch.Tensor, int, float, bool, str)):
-        return x.detach().cpu() if isinstance(x, torch.Tensor) else x
-    if isinstance(x, dict):
-        return {k: _ckpt_safe(v) for k, v in x.items()}
-    if isinstance(x, (list, tuple)):
-        return type(x)(_ckpt_safe(v) for v in x)
-    return None
+    checkpointed (it is saved as None), and a dict subclass (the _Bare
+    marker) is saved as a plain dict."""
+    return map_leaves(
+        lambda t: t.detach().cpu(), x,
+        other=lambda v: v if isinstance(v, (int, float, bool, str)) else None,
+        like=lambda c, vals: dict(zip(c, vals)) if isinstance(c, dict) else type(c)(vals))

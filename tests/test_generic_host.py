@@ -9,7 +9,7 @@ import torch
 
 
 def test_start_state_save_and_gather():
-    from madrona_learn.generic import _map_leaves, _zip_leaves
+    from madrona_learn.tree import map_leaves as _map_leaves, zip_leaves as _zip_leaves
     from madrona_learn.rnn import LSTM
     N, C, R, L = 6, 3, 4, 2
     lstm = LSTM(R, L, torch.float32)

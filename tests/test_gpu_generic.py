@@ -559,7 +559,7 @@ def _torch_tree(kind, dt):
 def test_torch_path_graph_replay_matches_eager(gpu, kind):
     """The torch path's whole update (rollout with the user's modules and
     the sim, GAE, the PPO update under autograd) captured in HIP graphs
-    (TrainingManager._update_torch: update 1 eager on the capture stream,
+    (TrainingManager._graphed: update 1 eager on the capture stream,
     update 2 captured, update 3 replayed) against the same tree trained
     eagerly (use_graph=False): parameters, Adam state, the rollout store and
     the loss metrics bit-identical after every update -- BackboneSeparate, a

@@ -1,5 +1,5 @@
 """Torch-path (generic.py) update timing, eager vs HIP-graph-replayed update
-(TrainingManager._update_torch: the whole update, else the PPO update only): BackboneSeparate MLP[256,256] x 2
+(TrainingManager._graphed: the whole update, else the PPO update only): BackboneSeparate MLP[256,256] x 2
 encoders, f32, N envs, T = 32, 2 epochs x 4 minibatches, synthetic env.
 usage: python tools/torch_path_bench.py [N] [updates]"""
 import os
