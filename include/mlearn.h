@@ -436,6 +436,79 @@ int mlearn_ppo_minibatch_fwd_bwd(const mlearn_mlp_policy* policy, const mlearn_r
                                  const mlearn_ppo_hparams* hp, void* workspace,
                                  mlearn_stream_t stream);
 
+/* ---------------------------------------------------------------------- */
+/* Importance-sampled trajectory minibatches                               */
+/* (TrainConfig.importance_sample_trajectories, ppo.py:407-435, 445-472,   */
+/* 220-252)                                                                */
+/* ---------------------------------------------------------------------- */
+/* Let n = C * B be the sequences of the view (B = N, C = T / bptt_len);
+ * sequence s is (chunk c = s / B, env b = s % B) and its store rows are
+ * (c * bptt_len + t) * ld + b.  Once per update S = num_minibatches *
+ * minibatch_size of them are drawn without replacement from softmax(score):
+ *
+ *  1. score_s = a_s / (float)bptt + v_s / (float)bptt with a_s = sum_t |adv|,
+ *     v_s = sum_t |values - return| (the returns column, or adv + values when
+ *     the view has none), summed sequentially over t in f32, no contraction:
+ *     host restatements agree bit for bit.
+ *  2. key_s = score_s + det_gumbel(sample_uniform(k0 ^ 0x494D5053,
+ *     k1 ^ 0x54524A53, env = s, step = *epoch_ctr, j = 0)) (Gumbel top-k =
+ *     jax.random.choice(replace=False, p)); (k0, k1) is the policy's update
+ *     key, *epoch_ctr the device epoch counter at the start of the update
+ *     (the word mlearn_minibatch_perm reads for epoch 0), read on the device;
+ *     the xor keeps the stream apart from the permutation's counters.  The
+ *     sample is the S largest keys (compared as f32 values, -0.0 == +0.0; a
+ *     tie goes to the lower id), written in ascending id order.
+ *  3. w_s = (1 / n) / softmax(score)_s = exp(lse - score_s) / n for all n
+ *     sequences, the log-sum-exp in double from per-block partials.
+ *  4. Epoch e visits sampled[perm_e], perm_e = mlearn_minibatch_perm(n = S);
+ *     the per-minibatch advantage statistics (mlearn_adv_stats over those
+ *     ids) stay unweighted (ppo.py:134-137).
+ *  5. The loss's three means take the weight of the row's sequence
+ *     (ppo.py:220-239): mean(w obj) per action key, mean(w vl), mean(w H);
+ *     gradient and 'Loss' are weighted, the other four metrics are not.
+ *
+ * mlearn_traj_importance_keys writes scores[n], keys[n] and, per block of 256
+ * sequences, lse_partials[block] = {max score, sum exp(score - max)}
+ * (2 * ceil(n / 256) doubles); mlearn_traj_importance_weights turns scores
+ * and partials into weights[n]. */
+int mlearn_traj_importance_keys(const mlearn_rollout_view* ro, uint32_t k0, uint32_t k1,
+                                const uint64_t* epoch_ctr, float* scores, float* keys,
+                                double* lse_partials, mlearn_stream_t stream);
+int mlearn_traj_importance_weights(const float* scores, const double* lse_partials, int32_t n,
+                                   float* weights, mlearn_stream_t stream);
+
+/* ids_out[k] = the ids of the k largest of keys[n] in ascending id order;
+ * keys compare as f32 values (-0.0 == +0.0, infinities allowed, NaN keys
+ * unspecified), equal keys at the threshold go to the lower ids.  A radix
+ * select over the order-preserving u32 image of the keys: ten launches, no
+ * host read-back, no allocation (workspace of
+ * mlearn_select_topk_workspace_bytes(n) bytes; -1 for n outside [1, 2^30]);
+ * the result does not depend on the arrival order of its (integer) atomics.
+ * 1 <= k <= n <= 2^30. */
+int64_t mlearn_select_topk_workspace_bytes(int32_t n);
+int mlearn_select_topk_f32(const float* keys, int32_t n, int32_t k, int32_t* ids_out,
+                           void* workspace, mlearn_stream_t stream);
+
+/* mlearn_ppo_minibatch_grad with per-sequence loss weights: minibatch row f
+ * (m = f % mb_size) takes w = seq_weight[mb_seq[m]] (seq_weight[n], by
+ * sequence id).  Every head's d loss takes hp->loss_scale * w (formed once
+ * per row in f32) where it takes hp->loss_scale, and the three sums of 'Loss'
+ * accumulate w * term; the 'Action Obj', 'Value Loss', 'Value Errors' and
+ * 'Entropy' outputs stay unweighted (ppo.py:351-362).  Runs the feature-split
+ * step kernel only (its own instantiation: the unweighted kernels are
+ * untouched): hp->step_kernel 0 or 1; 2 is MLEARN_EINVAL.  With all weights
+ * 1.0f the gradient and loss_out are bit-identical to
+ * mlearn_ppo_minibatch_grad's feature-split result.  Same workspace.  With
+ * loss_out set the unweighted step kernel runs first (the recorded metric
+ * vectors are its partials) and one more workgroup forms 'Loss': about one
+ * extra step launch, once per update. */
+int mlearn_ppo_minibatch_grad_weighted(const mlearn_mlp_policy* policy,
+                                       const mlearn_rollout_view* ro, const int32_t* mb_seq,
+                                       int32_t mb_size, const float* adv_stats,
+                                       const mlearn_ppo_hparams* hp, const float* seq_weight,
+                                       float* grad, float* loss_out, void* workspace,
+                                       mlearn_stream_t stream);
+
 /* Parameter layout of the flat f32 buffers (params, grads, Adam m/v):
  * per layer l: W_l [in_l][hidden], ln_scale_l [hidden], ln_bias_l [hidden];
  * then head W [hidden][A+C] (logits then the C = critic_bins critic outputs),

@@ -12,6 +12,10 @@
 //   wgrad   dW_l = X_l^T dZ_l for every weight in one launch (ppo_wgrad.h);
 //   reduce  fixed-order sum of slabs and partials into the flat f32 gradient
 //           and the loss / metric outputs (ppo_reduce.h).  No atomics.
+// mlearn_ppo_minibatch_grad_weighted (importance-sampled minibatches) runs the
+// feature split's weighted instantiation; when the metrics are recorded, the
+// unweighted step before it (the recorded metric partials) and one more
+// workgroup after the weight gradients ('Loss' from the weighted sums).
 //
 // Minibatch row f (time-major like mb['obs'] of shape [T/C, mb]):
 //   tl = f / mb, m = f % mb, seq = mb_seq[m], c = seq / N, b = seq % N,
@@ -78,7 +82,7 @@ template <typename T, int H>
 static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_view& ro,
                             const int32_t* mb_seq, int mb, const float* adv_st,
                             const mlearn_ppo_hparams& h, float* grad, float* loss_out, void* wsp,
-                            bool step_only, hipStream_t s) {
+                            bool step_only, hipStream_t s, const float* seq_weight = nullptr) {
     const int64_t M = (int64_t)mb * ro.bptt_len;
     WsK ws;
     carve(p, M, (char*)wsp, &ws);
@@ -93,11 +97,25 @@ static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_vie
     const bool rows16 = rows16_eligible(P, ws.Mp, head_cols(p), p.num_layers, H,
                                         std::is_same<T, bf16>::value);
     ML_REQUIRE(h.step_kernel >= 0 && h.step_kernel <= 2, "ppo: step_kernel %d", h.step_kernel);
-    ML_REQUIRE(h.step_kernel != 2 || rows16,
-               "ppo: step_kernel 2 (row-split) needs bf16, hidden 256, 2 layers, a scalar critic, "
-               "head width 32, obs_dim 64, <= 7 action groups and (padded) rows of 32768 or a "
-               "multiple of 256 from 65536");
-    if (rows16 && h.step_kernel != 1) {
+    ML_REQUIRE(h.step_kernel != 2 || (rows16 && !seq_weight), "%s",
+               seq_weight
+                   ? "ppo: step_kernel 2 (row-split) takes no per-sequence weights; the weighted "
+                     "step runs the feature-split kernel (step_kernel 0 or 1)"
+                   : "ppo: step_kernel 2 (row-split) needs bf16, hidden 256, 2 layers, a scalar critic, "
+                     "head width 32, obs_dim 64, <= 7 action groups and (padded) rows of 32768 or a "
+                     "multiple of 256 from 65536");
+    if (seq_weight) {
+        // the importance-weighted step: the feature split's weighted instantiation.
+        // In the minibatch that records metrics (once per update) the unweighted
+        // step runs first: its per-tile metric partials are the recorded 'Action
+        // Obj' .. 'Entropy' (unweighted by definition, ppo.py:351-362, and so the
+        // same bits as mlearn_ppo_minibatch_grad's); the weighted step then
+        // overwrites the operands and adds the three weighted sums of 'Loss'.
+        if (hp.metrics)
+            if (int rc = launch_step<T, H>(P, R, mb_seq, mb, M, adv_st, hp, ws, s)) return rc;
+        if (int rc = launch_step_weighted<T, H>(P, R, mb_seq, mb, M, adv_st, hp, ws, seq_weight, s))
+            return rc;
+    } else if (rows16 && h.step_kernel != 1) {
         ws.ncp = 2 * ws.ntiles;  // one column-partials row per 16-row tile
         if (rows16_cfg(ws.Mp).nt == 1) ws.nlp = 2 * ws.ntiles;  // one loss-partials row per wave
         launch_rows16(P, R, mb_seq, mb, M, adv_st, hp, ws, s);
@@ -114,6 +132,9 @@ static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_vie
     if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 1, ws), ws, hp, M, p.actions.num_groups,
                                  loss_out, make_layout(p), grad, h.grad_sumsq_out, s))
         return rc;
+    if (seq_weight && loss_out)  // 'Loss' from the weighted sums
+        hipLaunchKernelGGL(weighted_loss_kernel, dim3(1), dim3(256), 0, s, ws, hp, M,
+                           p.actions.num_groups, loss_out);
     return check_launch("ppo_minibatch_grad");
 }
 
@@ -230,7 +251,7 @@ static int validate_minibatch(const char* who, const mlearn_mlp_policy* policy,
 static int ppo_entry(const mlearn_mlp_policy* policy, const mlearn_rollout_view* ro,
                      const int32_t* mb_seq, int32_t mb_size, const float* adv_stats,
                      const mlearn_ppo_hparams* hp, float* grad, float* loss_out, void* workspace,
-                     bool step_only, mlearn_stream_t stream) {
+                     bool step_only, mlearn_stream_t stream, const float* seq_weight = nullptr) {
     int rc = validate_policy(policy);
     if (rc) return rc;
     rc = validate_minibatch("ppo", policy, ro, mb_seq, mb_size, adv_stats, hp, workspace);
@@ -240,7 +261,8 @@ static int ppo_entry(const mlearn_mlp_policy* policy, const mlearn_rollout_view*
     hipStream_t s = S(stream);
     return dispatch_th(policy->dtype, policy->hidden, [&](auto t, auto h) {
         return launch_minibatch<tag_t<decltype(t)>, h>(*policy, *ro, mb_seq, mb_size, adv_stats,
-                                                       *hp, grad, loss_out, workspace, step_only, s);
+                                                       *hp, grad, loss_out, workspace, step_only, s,
+                                                       seq_weight);
     });
 }
 
@@ -250,6 +272,17 @@ int mlearn_ppo_minibatch_grad(const mlearn_mlp_policy* policy, const mlearn_roll
                               void* workspace, mlearn_stream_t stream) {
     return ppo_entry(policy, ro, mb_seq, mb_size, adv_stats, hp, grad, loss_out, workspace, false,
                      stream);
+}
+
+int mlearn_ppo_minibatch_grad_weighted(const mlearn_mlp_policy* policy,
+                                       const mlearn_rollout_view* ro, const int32_t* mb_seq,
+                                       int32_t mb_size, const float* adv_stats,
+                                       const mlearn_ppo_hparams* hp, const float* seq_weight,
+                                       float* grad, float* loss_out, void* workspace,
+                                       mlearn_stream_t stream) {
+    ML_REQUIRE(seq_weight, "ppo: null seq_weight");
+    return ppo_entry(policy, ro, mb_seq, mb_size, adv_stats, hp, grad, loss_out, workspace, false,
+                     stream, seq_weight);
 }
 
 int64_t mlearn_lstm_ppo_workspace_bytes(const mlearn_mlp_policy* policy, const mlearn_lstm* lstm,

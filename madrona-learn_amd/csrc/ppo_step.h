@@ -100,17 +100,69 @@ __device__ inline void store_rows16(bf16* rowp, int w, uint32_t (&wd)[NBW][8], i
 template <int NBW, bool RESTORE>
 __device__ inline void store_rows16(float*, int, f2 (&)[NBW][8], int) {}
 
+// The per-sequence loss weights of the importance-sampled update
+// (mlearn_ppo_minibatch_grad_weighted): the step kernel's last argument, empty
+// in the unweighted instantiations (WT = false), whose arguments, code and
+// results it therefore leaves where they were.
+template <bool WT> struct StepWeights {};
+template <> struct StepWeights<true> {
+    const float* seq_weight;  // [C * N], by sequence id
+};
+// Weight of minibatch row f: seq_weight[mb_seq[f % mb]] (store_row's index math).
+__device__ inline float row_weight(const StepWeights<true>& sw, const int32_t* mb_seq, int mb,
+                                   int64_t f) {
+    const uint32_t fu = (uint32_t)f, mbu = (uint32_t)mb;
+    return sw.seq_weight[mb_seq[fu - (fu / mbu) * mbu]];
+}
+
+// What the weighted step adds to the loss tasks of a thread.  The heads
+// (ppo_defs.h) run as they are, on a copy of the hyper-parameters whose
+// loss_scale is hp.loss_scale * w of the task's row (formed once per row task,
+// f32), and into the same accumulators, so the metric sums stay unweighted
+// (the recorded metric slots themselves come from an unweighted launch of the
+// same minibatch, launch_minibatch: the two instantiations need not contract
+// their sums of squares alike).
+// The three sums of 'Loss' (ppo.py:220-239) come from the prefix values the
+// accumulators pass through: with S_i the sum after task i (S_0 = 0),
+//   sum_i w_i (S_i - S_{i-1}) = w_n S_n + sum_{i<n} (w_i - w_{i+1}) S_i,
+// which is w S_n exactly when all weights are equal.
+template <bool WT> struct LossWeights {};  // unweighted: nothing (the heads see hp itself)
+template <> struct LossWeights<true> {
+    HpK hl;
+    float base;                          // hp.loss_scale
+    float pw = 0.f;                      // weight of the previous task's row
+    float so = 0.f, se = 0.f, sv = 0.f;  // weighted surrogate / entropy / value-loss sums
+    __device__ void init(const HpK& hp) {
+        hl = hp;
+        base = hp.loss_scale;
+    }
+    __device__ void begin(float w, const LossAcc& m) {  // before a task of a row of weight w
+        const float d = pw - w;
+        so += d * m.sobjw;
+        se += d * m.sentw;
+        sv += d * m.svl;
+        pw = w;
+        hl.loss_scale = base * w;
+    }
+    __device__ void finish(const LossAcc& m) {  // after the thread's last task
+        so += pw * m.sobjw;
+        se += pw * m.sentw;
+        sv += pw * m.svl;
+    }
+};
+
 // RTW row tiles of 32 rows per workgroup (kFused): waves w and w + W * rt own
 // the same features of different rows, released by the same barriers, so
 // their weight-fragment loads of every product meet in the CU's L1.
 // HLG: the HL-Gauss critic (PolicyK.CK = 1) -- a template parameter, so that
 // the scalar / two-hot instantiations compile to the code they had before it
 // (as a runtime branch it moved their register allocation).
+// WT: the importance-weighted step, its own instantiation for the same reason.
 template <typename T, int H, int L, int MODE = kFused, int HC = MLEARN_HEAD_COLS, int RTW = 1,
-          bool HLG = false>
+          bool HLG = false, bool WT = false>
 __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_waves_per_eu(ML_STEP_WAVES, 8))) void ppo_step_kernel(
     PolicyK P, RolloutK ro, const int32_t* __restrict__ mb_seq, int mb, int64_t M,
-    const float* __restrict__ adv_st, HpK hp, WsK ws, RecK rec) {
+    const float* __restrict__ adv_st, HpK hp, WsK ws, RecK rec, StepWeights<WT> sw) {
     constexpr bool kFwd = MODE != kHeads;                     // runs the trunk forward
     constexpr bool kLoss = MODE == kFused || MODE == kHeads;  // heads + loss
     constexpr bool kBwd = MODE == kFused || MODE == kTrunkBwd;  // trunk backward
@@ -170,6 +222,9 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
     const int64_t tsr = tlive ? store_row(ro, mb_seq, mb, row0 + tr) : 0;
     int t_act = 0;
     float t_lp = 0.f, t_adv = 0.f, t_ret = 0.f, t_val = 0.f;
+    [[maybe_unused]] float t_w = 1.f;
+    if constexpr (WT)
+        if (tlive) t_w = row_weight(sw, mb_seq, mb, row0 + tr);
     if (tlive) {
         t_adv = ro.adv[tsr];
         if (tg < K) {
@@ -347,6 +402,8 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
     // ---- loss: one (row, group | value) task per thread (ppo.py:129-262) ----
     {
         LossAcc m;
+        [[maybe_unused]] LossWeights<WT> lw;
+        if constexpr (WT) lw.init(hp);
         bool did = false;  // this lane ran a task (waves without any skip the reductions)
         const float as0 = adv_st[0], as1 = adv_st[1];
         const float* vn = hp.norm_vals ? adv_st + 2 : nullptr;
@@ -373,7 +430,9 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
             float olp, adv, ret, oval;
             if (task == tid) {
                 act = t_act, olp = t_lp, adv = t_adv, ret = t_ret, oval = t_val;
+                if constexpr (WT) lw.begin(t_w, m);
             } else {
+                if constexpr (WT) lw.begin(row_weight(sw, mb_seq, mb, f), m);
                 const int64_t q = store_row(ro, mb_seq, mb, f);
                 adv = ro.adv[q];
                 act = g < K ? ro.actions[q * K + g] : 0;
@@ -383,9 +442,15 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
             }
             if (g < K) {
                 if (hp.norm_adv) adv = (adv - as0) * as1;
+                if constexpr (WT)
+                    loss_group(lw.hl, lr + P.off[g], P.off[g + 1] - P.off[g], act, olp, adv,
+                               hp.ecoef[g], hp.objw[g], m);
+                else
                 loss_group(hp, lr + P.off[g], P.off[g + 1] - P.off[g], act, olp, adv, hp.ecoef[g],
                            hp.objw[g], m);
             } else {
+                if constexpr (WT) loss_value(lw.hl, lr, P.A, HC, ret, oval, m, vn);
+                else
                 loss_value(hp, lr, P.A, HC, ret, oval, m, vn);
             }
         }
@@ -403,6 +468,15 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
                     continue;
                 }
                 const float R = ret_at(ro, store_row(ro, mb_seq, mb, f));
+                if constexpr (WT) lw.begin(row_weight(sw, mb_seq, mb, f), m);
+                if constexpr (WT) {
+                    if constexpr (HLG)
+                        loss_value_hlgauss_g<G>(lw.hl, lr, P.A, P.CB, HC, bins, bounds,
+                                                P.head_b[HC + 2 * P.CB + 1], lgp + rr * LGS, R, sub,
+                                                m);
+                    else
+                        loss_value_twohot_g<G>(lw.hl, lr, P.A, P.CB, HC, bins, R, sub, m);
+                } else
                 if constexpr (HLG)  // smoothness ends the table; scratch = the row's head partials
                     loss_value_hlgauss_g<G>(hp, lr, P.A, P.CB, HC, bins, bounds,
                                             P.head_b[HC + 2 * P.CB + 1], lgp + rr * LGS, R, sub, m);
@@ -410,10 +484,17 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
                     loss_value_twohot_g<G>(hp, lr, P.A, P.CB, HC, bins, R, sub, m);
             }
         }
-        const float vals[kLossSlots] = {m.sobj, m.qobj, m.mnobj, m.mxobj, m.svl, m.qvl, m.mnvl,
-                                        m.mxvl, m.serr, m.qerr, m.mnerr, m.mxerr, m.sent, m.qent,
-                                        m.mnent, m.mxent, m.sentw, m.sobjw, 0.f, 0.f};
-        constexpr int kUsed = 18;  // slots 18.. are padding
+        typedef typename std::conditional<WT, float, const float>::type slot_t;
+        slot_t vals[kLossSlots] = {m.sobj, m.qobj, m.mnobj, m.mxobj, m.svl, m.qvl, m.mnvl,
+                                   m.mxvl, m.serr, m.qerr, m.mnerr, m.mxerr, m.sent, m.qent,
+                                   m.mnent, m.mxent, m.sentw, m.sobjw, 0.f, 0.f};
+        if constexpr (WT) {  // the three weighted sums of 'Loss' (loss_block<true>)
+            lw.finish(m);
+            vals[16] = lw.se;
+            vals[17] = lw.so;
+            vals[18] = lw.sv;
+        }
+        constexpr int kUsed = WT ? 19 : 18;  // the slots above are padding
         if (!hp.metrics) {
         } else if (__any(did)) {
 #pragma unroll
@@ -438,7 +519,9 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
             const double x = lred[u * kLossSlots + tid];
             v = kind == 2 ? fmin(v, x) : (kind == 3 ? fmax(v, x) : v + x);
         }
-        ws.loss_part[(int64_t)tile * kLossSlots + tid] = v;
+        // (the weighted step writes its three sums of 'Loss' only: the metric
+        // slots are the unweighted launch's that ran before it, launch_minibatch)
+        if (!WT || (tid >= 16 && tid < 19)) ws.loss_part[(int64_t)tile * kLossSlots + tid] = v;
     }
     STAMP(8);
     // the backward head product's weight fragments go out before the stores below
@@ -642,22 +725,24 @@ __global__ __launch_bounds__(64 * StepCfg<H>::W * RTW) __attribute__((amdgpu_wav
 #ifndef ML_STEP_RTW
 #define ML_STEP_RTW 1  // row tiles per workgroup of the fused MLP step (kFused; 2 measured slower)
 #endif
-template <typename T, int H, int L, int MODE, int HC, bool HLG = false>
+template <typename T, int H, int L, int MODE, int HC, bool HLG = false, bool WT = false>
 static int launch_step_hc(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
                           int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
-                          hipStream_t s, const RecK& rec) {
+                          hipStream_t s, const RecK& rec, StepWeights<WT> sw = {}) {
     // ntiles = Mp / 32 is even (Mp is a multiple of 64)
     constexpr int RTW = (MODE == kFused && StepCfg<H>::W * ML_STEP_RTW <= 16) ? ML_STEP_RTW : 1;
     // (only the phases with the loss have an HL-Gauss instantiation)
     if constexpr (!HLG && (MODE == kFused || MODE == kHeads))
-        if (P.CK) return launch_step_hc<T, H, L, MODE, HC, true>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec);
-    auto k = ppo_step_kernel<T, H, L, MODE, HC, RTW, HLG>;
+        if (P.CK)
+            return launch_step_hc<T, H, L, MODE, HC, true, WT>(P, R, mb_seq, mb, M, adv_st, hp, ws,
+                                                               s, rec, sw);
+    auto k = ppo_step_kernel<T, H, L, MODE, HC, RTW, HLG, WT>;
     // (once per instantiation and device, kept out of graph capture)
     if (int rc = set_lds_attr((const void*)k, 160 * 1024, "ppo_step")) return rc;
     const size_t lds = step_lds<T, H, L, HC, RTW, HLG>();
     const int threads = 64 * StepCfg<H>::W * RTW;
     hipLaunchKernelGGL(k, dim3(ws.ntiles / RTW), dim3(threads), lds, s, P, R, mb_seq, mb, M,
-                       adv_st, hp, ws, rec);
+                       adv_st, hp, ws, rec, sw);
     return MLEARN_OK;
 }
 // The step kernel of the policy's depth and head width (MODE: the whole
@@ -670,6 +755,19 @@ static int launch_step(const PolicyK& P, const RolloutK& R, const int32_t* mb_se
         constexpr int L = l;
         return dispatch_head(P.HC, [&](auto hc) {
             return launch_step_hc<T, H, L, MODE, hc>(P, R, mb_seq, mb, M, adv_st, hp, ws, s, rec);
+        });
+    });
+}
+// The importance-weighted whole step (kFused): row weights seq_weight[mb_seq[f % mb]].
+template <typename T, int H>
+static int launch_step_weighted(const PolicyK& P, const RolloutK& R, const int32_t* mb_seq, int mb,
+                                int64_t M, const float* adv_st, const HpK& hp, const WsK& ws,
+                                const float* seq_weight, hipStream_t s) {
+    return dispatch_layers(P.L, [&](auto l) {
+        constexpr int L = l;
+        return dispatch_head(P.HC, [&](auto hc) {
+            return launch_step_hc<T, H, L, kFused, hc, false, true>(
+                P, R, mb_seq, mb, M, adv_st, hp, ws, s, RecK{}, StepWeights<true>{seq_weight});
         });
     });
 }

@@ -71,6 +71,7 @@ template <> struct WgFrag<float> {
 };
 
 __device__ inline void colsum_block(const WsK& ws, int bx, int c);
+template <bool WEIGHTED = false>
 __device__ inline void loss_block(const WsK& ws, const HpK& hp, int64_t M, int K, float* out);
 
 // Weight-gradient tile (i0, j0) of job J over its split's rows.
@@ -426,6 +427,10 @@ __device__ inline void colsum_block(const WsK& ws, int bx, int c) {
 // loss_out: five Metric vectors {mean, m2, min, max, count} in the order of
 // PPO.add_metrics (ppo.py:95-106): 'Loss' (scalar: {loss, 0, loss, loss, 1}),
 // 'Action Obj', 'Value Loss', 'Value Errors', 'Entropy'.
+// WEIGHTED (the importance-weighted step, weighted_loss_kernel): the value-loss
+// term of 'Loss' from the sum of w * vl (slot 18; slots 16 and 17 then hold
+// the weighted sums too); the four metric vectors stay unweighted.
+template <bool WEIGHTED>
 __device__ inline void loss_block(const WsK& ws, const HpK& hp, int64_t M, int K, float* out) {
     __shared__ double sh[4][kLossSlots];
     __shared__ double tot[kLossSlots];
@@ -467,7 +472,7 @@ __device__ inline void loss_block(const WsK& ws, const HpK& hp, int64_t M, int K
     __syncthreads();
     if (tid == 0) {
         const double nk = (double)M * K, n = (double)M;
-        const double vl_mean = tot[4] / n;
+        const double vl_mean = tot[WEIGHTED ? 18 : 4] / n;
         // loss = -sum_key mean(obj_key) + c_v * mean(vl) - sum_key c_e[key] * mean(H_key)
         // (ppo.py:221-252); the per-sub-action weights K / K_key are in slots 16, 17
         const double loss = -tot[17] / nk + hp.vcoef * vl_mean - tot[16] / nk;
@@ -487,6 +492,14 @@ __device__ inline void loss_block(const WsK& ws, const HpK& hp, int64_t M, int K
             out[5 + 5 * m + 4] = (float)cnt[m];
         }
     }
+}
+
+// mlearn_ppo_minibatch_grad_weighted: loss_out once more from the same
+// partials in the same order, 'Loss' now from the weighted sums (its own
+// launch after the weight-gradient launch, whose code stays as it is).
+__global__ __launch_bounds__(256) void weighted_loss_kernel(WsK ws, HpK hp, int64_t M, int K,
+                                                            float* loss_out) {
+    loss_block<true>(ws, hp, M, K, loss_out);
 }
 
 // The gradient launches: weight-gradient tiles, column partials and loss

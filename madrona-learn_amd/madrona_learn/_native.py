@@ -219,6 +219,14 @@ _SIGNATURES = {
                                                    c_int32, c_int32]),
     "mlearn_ppo_minibatch_grad": (c_int32, [POINTER(MlpPolicy), POINTER(RolloutView), _P,
                                             c_int32, _P, POINTER(PPOHparams), _P, _P, _P, _S]),
+    "mlearn_ppo_minibatch_grad_weighted": (c_int32, [POINTER(MlpPolicy), POINTER(RolloutView), _P,
+                                                     c_int32, _P, POINTER(PPOHparams), _P, _P, _P,
+                                                     _P, _S]),
+    "mlearn_traj_importance_keys": (c_int32, [POINTER(RolloutView), c_uint32, c_uint32, _P, _P, _P,
+                                              _P, _S]),
+    "mlearn_traj_importance_weights": (c_int32, [_P, _P, c_int32, _P, _S]),
+    "mlearn_select_topk_workspace_bytes": (c_int64, [c_int32]),
+    "mlearn_select_topk_f32": (c_int32, [_P, c_int32, c_int32, _P, _P, _S]),
     "mlearn_ppo_minibatch_fwd_bwd": (c_int32, [POINTER(MlpPolicy), POINTER(RolloutView), _P,
                                                c_int32, _P, POINTER(PPOHparams), _P, _S]),
     "mlearn_param_count": (c_int64, [POINTER(MlpPolicy)]),

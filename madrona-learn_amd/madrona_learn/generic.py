@@ -623,9 +623,12 @@ class TorchPPO(PPO):
             out["rnn_start"] = map_leaves(lambda x: x[c, b], s.torch_start)
         return out
 
-    def _loss(self, ps, mbd, adv_stats):
+    def _loss(self, ps, mbd, adv_stats, weights=None):
         """ppo.py:129-262 on one minibatch (torch autograd through the user's
-        modules; action_stats on the HIP kernel)."""
+        modules; action_stats on the HIP kernel).  ``weights`` [M]
+        (importance_sample_trajectories): the sequences' loss weights, broadcast
+        as [1, M, 1] into the three means of the loss (ppo.py:220-239); the
+        recorded arrays stay unweighted (ppo.py:351-362)."""
         ac = ps.actor_critic
         obs = ps.codec.decode(mbd["obs"])
         T, M = mbd["dones"].shape
@@ -658,13 +661,16 @@ class TorchPPO(PPO):
         hi = torch.full_like(ratio, 1.0 + self.clip)
         surr2 = a * torch.minimum(torch.maximum(ratio, lo), hi)
         obj = torch.minimum(surr1, surr2)
+        w3 = None if weights is None else weights.reshape(1, M, 1)
+        obj_w = obj if w3 is None else w3 * obj
+        ent_w = ent if w3 is None else w3 * ent
         action_obj = 0.0
         entropy_term = 0.0
         off = 0
         for grp, c in zip(self.groups, self.ecoef):
             k = grp.cols
-            action_obj = action_obj + obj[..., off:off + k].mean()
-            entropy_term = entropy_term + c * ent[..., off:off + k].mean()
+            action_obj = action_obj + obj_w[..., off:off + k].mean()
+            entropy_term = entropy_term + c * ent_w[..., off:off + k].mean()
             off += k
         R = mbd["returns"].float()
         verr = None
@@ -695,7 +701,7 @@ class TorchPPO(PPO):
                 vl = 0.5 * q * q + (ae - q)
             else:  # optax.l2_loss
                 vl = 0.5 * e * e
-        value_loss = vl.mean()
+        value_loss = vl.mean() if w3 is None else (w3[..., 0] * vl).mean()
         loss = -action_obj + self.vcoef * value_loss - entropy_term
         with torch.no_grad():
             met = {"Loss": loss.detach(), "Action Obj": obj.detach(), "Value Loss": vl.detach(),
@@ -713,7 +719,9 @@ class TorchPPO(PPO):
                 mbd = self._minibatch(seqs)
                 ps.grads.zero_()
                 stats = self.vn_rec[e, m] if self.vnorm else self.adv_stats[e, m]
-                loss, met = self._loss(ps, mbd, stats)
+                # importance_sample_trajectories: the weights of the minibatch's sequences
+                w = self.imp_weights[seqs.long()] if self.imp else None
+                loss, met = self._loss(ps, mbd, stats, w)
                 sc = ts.scaler
                 if sc is None:
                     (loss * self.loss_scale).backward()

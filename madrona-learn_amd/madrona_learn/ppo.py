@@ -8,6 +8,13 @@ parallel gradient all-reduce, and one native optimizer step
 (ppo.py:283-338).  It is a generator: it yields ('allreduce', tensor) at
 every collective so the caller can run it eagerly or capture the compute
 between collectives into HIP graphs.
+
+With ``TrainConfig.importance_sample_trajectories`` (ppo.py:407-435) the
+update first draws ``importance_sample_num_minibatches * minibatch_size`` of
+the C*B sequences without replacement from softmax(mean |advantage| + mean
+|value error|) on the device, every epoch permutes that sample, and every
+minibatch's loss takes the per-sequence weights (1/n) / softmax (the contract:
+include/mlearn.h, "Importance-sampled trajectory minibatches").
 """
 
 from dataclasses import dataclass
@@ -88,10 +95,17 @@ class PPO(AlgoBase):  # ppo.py:49-106
         """The minibatch plan and the per-update statistics buffers both update
         paths share (allocated once: graph-capture safe)."""
         algo = cfg.algo
-        if cfg.filter_advantages or cfg.importance_sample_trajectories:
+        if cfg.filter_advantages:
             raise NotImplementedError(
-                "filter_advantages / importance_sample_trajectories (ppo.py:374-435) are "
-                "non-default modes outside the fused path")
+                "filter_advantages (ppo.py:374-406): its traj_weights has shape (num_points,) "
+                "and does not broadcast against the [1, mb, K] objectives for K > 1, and its "
+                "minibatch count depends on the data, which defeats HIP-graph capture of the "
+                "update")
+        self.imp = bool(cfg.importance_sample_trajectories)
+        if self.imp:
+            self._plan_importance(cfg, view, dp, device)
+            self._plan_stats(cfg, view, dp, device, train_state, policy_idx)
+            return
         C = cfg.num_bptt_chunks
         self.bptt = cfg.steps_per_update // C
         # minibatch_size is GLOBAL (sequences per optimizer step of this
@@ -109,6 +123,57 @@ class PPO(AlgoBase):  # ppo.py:49-106
         self.num_mb = self.num_seq // self.mb
         self.E = int(algo.num_epochs)
         self.perm = torch.zeros((self.E, self.num_seq), dtype=torch.int32, device=device)
+        self._plan_stats(cfg, view, dp, device, train_state, policy_idx)
+
+    def _plan_importance(self, cfg, view, dp, device):
+        """The plan of importance_sample_trajectories (ppo.py:407-435): one
+        draw of S = importance_sample_num_minibatches * minibatch_size of the
+        n = C B sequences per update, ``perm`` (E, S) holds every epoch's order
+        of the sampled ids."""
+        algo = cfg.algo
+        ref = "importance_sample_trajectories (ppo.py:407-435)"
+        if not cfg.compute_advantages:
+            raise NotImplementedError(
+                f"{ref} with compute_advantages=False: the scores need the advantages, which "
+                "the rollout then does not compute")
+        if cfg.normalize_values:
+            raise NotImplementedError(
+                f"{ref} with normalize_values: the reference then scores normalised values "
+                "against unnormalised returns; that quirk is not restated")
+        if dp.world_size > 1:
+            raise NotImplementedError(
+                f"{ref} under data parallelism ({dp.world_size} ranks train this policy): the "
+                "softmax and the draw would have to be global")
+        C = cfg.num_bptt_chunks
+        self.bptt = cfg.steps_per_update // C
+        self.num_seq = C * view.N
+        self.mb = int(algo.minibatch_size)
+        self.num_mb = int(cfg.importance_sample_num_minibatches)
+        if self.num_mb <= 0:  # the reference asserts it (ppo.py:408)
+            raise ValueError(f"{ref} needs importance_sample_num_minibatches > 0, got "
+                             f"{self.num_mb}")
+        self.num_sampled = S = self.num_mb * self.mb
+        n = self.num_seq
+        if S >= n:  # the reference asserts it (ppo.py:409)
+            raise ValueError(
+                f"{ref} draws importance_sample_num_minibatches x minibatch_size = {S} "
+                f"sequences, which must be fewer than the {n} there are")
+        self.E = int(algo.num_epochs)
+        self.perm = torch.zeros((self.E, S), dtype=torch.int32, device=device)
+        # each epoch's permutation of [0, S) (perm[e] = imp_sample[imp_order[e]])
+        self.imp_order = torch.zeros((self.E, S), dtype=torch.int32, device=device)
+        self.imp_scores = torch.zeros(n, dtype=torch.float32, device=device)
+        self.imp_keys = torch.zeros(n, dtype=torch.float32, device=device)
+        self.imp_weights = torch.zeros(n, dtype=torch.float32, device=device)
+        self.imp_sample = torch.zeros(S, dtype=torch.int32, device=device)
+        self.imp_lse = torch.zeros(2 * ((n + 255) // 256), dtype=torch.float64, device=device)
+        nbytes = int(nat.lib().mlearn_select_topk_workspace_bytes(n))
+        if nbytes < 0:
+            raise ValueError(f"{ref}: {n} sequences exceed the selection's 2^30")
+        self.imp_ws = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+    def _plan_stats(self, cfg, view, dp, device, train_state, policy_idx):
+        """The per-minibatch statistics buffers of either plan."""
         self.adv_part = torch.zeros((self.E, self.num_mb * 66), dtype=torch.float64,
                                     device=device)
         self.adv_stats = torch.zeros((self.E, self.num_mb, 2), dtype=torch.float32, device=device)
@@ -144,6 +209,11 @@ class PPO(AlgoBase):  # ppo.py:49-106
         self._plan_minibatches(cfg, view, dp, dev, train_state, policy_idx)
         rows = self.mb * self.bptt
         self.lstm = policy_state.lstm_desc
+        if self.imp and self.lstm is not None:
+            raise NotImplementedError(
+                "importance_sample_trajectories with a recurrent policy on the fused path: "
+                "mlearn_lstm_ppo_minibatch_grad takes no per-sequence weights (the torch path "
+                "trains recurrent policies in this mode)")
         if self.lstm is not None:
             if start_states is None:
                 raise ValueError("a recurrent policy needs the rollout's rnn_start_states")
@@ -224,9 +294,28 @@ class PPO(AlgoBase):  # ppo.py:49-106
         L = nat.lib()
         strm = nat.stream_handle()
         k0, k1 = train_state.update_prng_key
+        if self.imp:
+            # the update's one draw (keys -> select -> weights), before the epochs'
+            # permutations of the sample; all on the device
+            n, S = self.num_seq, self.num_sampled
+            nat.check(L.mlearn_traj_importance_keys(
+                self.view, k0, k1, nat.ptr(epoch_ctr), nat.ptr(self.imp_scores),
+                nat.ptr(self.imp_keys), nat.ptr(self.imp_lse), strm), "traj_importance_keys")
+            nat.check(L.mlearn_select_topk_f32(nat.ptr(self.imp_keys), n, S,
+                                               nat.ptr(self.imp_sample), nat.ptr(self.imp_ws),
+                                               strm), "select_topk")
+            nat.check(L.mlearn_traj_importance_weights(
+                nat.ptr(self.imp_scores), nat.ptr(self.imp_lse), n, nat.ptr(self.imp_weights),
+                strm), "traj_importance_weights")
         for e in range(self.E):
-            nat.check(L.mlearn_minibatch_perm(k0, k1, nat.ptr(epoch_ctr), e, self.dp.rank,
-                                              self.num_seq, nat.ptr(self.perm[e]), strm), "perm")
+            if self.imp:
+                nat.check(L.mlearn_minibatch_perm(k0, k1, nat.ptr(epoch_ctr), e, self.dp.rank, S,
+                                                  nat.ptr(self.imp_order[e]), strm), "perm")
+                torch.index_select(self.imp_sample, 0, self.imp_order[e], out=self.perm[e])
+            else:
+                nat.check(L.mlearn_minibatch_perm(k0, k1, nat.ptr(epoch_ctr), e, self.dp.rank,
+                                                  self.num_seq, nat.ptr(self.perm[e]), strm),
+                          "perm")
             nat.check(L.mlearn_adv_stats(self.view, nat.ptr(self.perm[e]), self.num_mb, self.mb,
                                          nat.ptr(self.adv_part[e]), strm), "adv_stats")
             if self.vnorm:
@@ -278,6 +367,12 @@ class PPO(AlgoBase):  # ppo.py:49-106
                         nat.ptr(seqs), self.mb, nat.ptr(stats), self.hp,
                         nat.ptr(train_state.grads), lo, nat.ptr(self.ws), strm),
                         "lstm_ppo_minibatch_grad")
+                elif self.imp:
+                    nat.check(L.mlearn_ppo_minibatch_grad_weighted(
+                        policy_state.desc, self.view, nat.ptr(seqs), self.mb,
+                        nat.ptr(stats), self.hp, nat.ptr(self.imp_weights),
+                        nat.ptr(train_state.grads), lo, nat.ptr(self.ws), strm),
+                        "ppo_minibatch_grad_weighted")
                 else:
                     nat.check(L.mlearn_ppo_minibatch_grad(
                         policy_state.desc, self.view, nat.ptr(seqs), self.mb,
