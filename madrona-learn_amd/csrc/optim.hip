@@ -5,9 +5,28 @@
 //   -> LayerNorm renorm so that |scale|^2 + |bias|^2 = features (ppo.py:312-338)
 //   -> refresh of the compute-dtype weight copies the MLP kernels read
 //      (transposed [out][in] and [in][out] images, padded head).
-// Three short launches over the flat 90K-float parameter vector; global
-// reductions go through fixed-order double partials that every consumer
+// Global reductions go through fixed-order double partials that every consumer
 // block re-reduces identically (deterministic, no finishing launches).
+//
+// Each stage is written once, as a __device__ function: sumsq_block (gradient
+// sum of squares), global_norm, adam_update (clip + Adam), slot_accumulate +
+// slot_partial (the per-block projection partials), slot_totals and
+// project_value.  Two drivers call them: the split launches
+// (sumsq_partial_kernel, adam_kernel, project_kernel: the library's choice,
+// three short launches over the flat 90K-float parameter vector) and the
+// opt-in one-launch form (optim_fused_kernel), which differ only in how a
+// partial is loaded and stored (plain, or agent scope inside one launch), in
+// which threads reduce (all 256, or the first 256 of 1024) and in when results
+// are stored.  Their results are bit-identical, which takes two rules:
+//  * `#pragma clang fp contract(off)` is lexical, not inherited by an inlined
+//    callee: every stage that multiplies and adds carries it itself, so each
+//    operation rounds once as written whatever the caller's schedule (an fma's
+//    choice of which product to keep unrounded otherwise differs per caller);
+//  * a stage with a barrier is called by every thread of the workgroup and
+//    takes an `active` predicate for the threads that reduce.
+// The summation orders are each stage's own (((a+b)+c)+d in the norm partials
+// and the slot totals, (a+b)+(c+d) in global_norm and the slot partials) and
+// are what tests/test_gpu_optim_bits.py pins.
 
 #include "common.h"
 #include "dispatch.h"
@@ -50,30 +69,59 @@ static CopiesK make_copies(const mlearn_mlp_policy& p, const mlearn_lstm* r = nu
     return c;
 }
 
-__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, int64_t n,
-                                                            double* part) {
-#pragma clang fp contract(off)  // (one rounding per operation: optim_fused_kernel's bits)
-    __shared__ double sh[4];
-    double s = 0;
-    // eight of this thread's strided elements in flight at a time, summed in index order
-    const int64_t st = (int64_t)gridDim.x * 256;
-    for (int64_t i0 = blockIdx.x * 256 + threadIdx.x; i0 < n; i0 += 8 * st) {
-        float x[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) x[u] = i0 + u * st < n ? g[i0 + u * st] : 0.f;
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-            if (i0 + u * st < n) {
-                const double v = x[u];
-                s += v * v;
-            }
-    }
-    s = wave_sum64d(s);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((sh[0] + sh[1]) + sh[2]) + sh[3];
+// A partial is loaded and stored plainly between launches and with agent scope
+// (sc1) where it is handed from workgroup to workgroup inside one launch.
+__device__ inline uint64_t ld_sc1(const uint64_t* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+__device__ inline double ld_sc1d(const double* p) {
+    return __builtin_bit_cast(double, ld_sc1((const uint64_t*)p));
+}
+__device__ inline void st_sc1d(double* p, double x) {
+    __hip_atomic_store((uint64_t*)p, __builtin_bit_cast(uint64_t, x), __ATOMIC_RELAXED,
+                       __HIP_MEMORY_SCOPE_AGENT);
+}
+template <bool SC1> __device__ inline double ld_part(const double* p) {
+    return SC1 ? ld_sc1d(p) : *p;
+}
+template <bool SC1> __device__ inline void st_part(double* p, double x) {
+    if (SC1) st_sc1d(p, x); else *p = x;
 }
 
+// part[k] = the sum of squares of g[0..n) that falls to norm block k of
+// nblocks: the 256 `active` threads (threadIdx.x < 256) each take eight strided
+// elements in flight at a time, summed in index order.  One barrier: every
+// thread of the workgroup calls it (and syncs before calling it again).
+template <bool SC1>
+__device__ __forceinline__ void sumsq_block(const float* __restrict__ g, int64_t n, int k,
+                                            int nblocks, bool active, double* part) {
+#pragma clang fp contract(off)
+    __shared__ double sh[4];
+    if (active) {
+        double s = 0;
+        const int64_t st = (int64_t)nblocks * 256;
+        for (int64_t i0 = k * 256 + threadIdx.x; i0 < n; i0 += 8 * st) {
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = i0 + u * st < n ? g[i0 + u * st] : 0.f;
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (i0 + u * st < n) {
+                    const double v = x[u];
+                    s += v * v;
+                }
+        }
+        s = wave_sum64d(s);
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) st_part<SC1>(part + k, ((sh[0] + sh[1]) + sh[2]) + sh[3]);
+}
+
+__global__ __launch_bounds__(256) void sumsq_partial_kernel(const float* __restrict__ g, int64_t n,
+                                                            double* part) {
+    sumsq_block<false>(g, n, blockIdx.x, gridDim.x, true, part);
+}
 
 // tensor id of parameter p for the projection partials: 2*l = W_l, 2*l+1 =
 // LN_l, 2L + 4*which + gate = LSTM gate kernel, -1 = not projected
@@ -91,6 +139,11 @@ __device__ inline int proj_slot(const LayoutK& k, int64_t p) {
     return p < k.s_off[l] ? 2 * l : 2 * l + 1;
 }
 
+// recurrent layouts: the alignment padding before the LSTM segment is not a parameter
+__device__ inline bool is_padding(const LayoutK& k, int64_t p) {
+    return k.lstm_H && p >= k.mlp_total && p < k.lstm_off;
+}
+
 // one parameter per thread up to 512 x 256 parameters (the headline MLP's
 // 89 883 take 352 blocks), so each thread's update is one memory latency
 // (adam 7.1 -> 6.0 us at the headline config)
@@ -100,24 +153,29 @@ __device__ inline int proj_slot(const LayoutK& k, int64_t p) {
 constexpr int kAdamBlocks = ML_ADAM_BLOCKS;
 
 // Global gradient norm from npart partials (every block computes it the same
-// way: thread i sums partials i, i + 256, ..., then a fixed butterfly).
-__device__ inline float global_norm(const double* gpart, int64_t npart) {
+// way: active thread i < 256 sums partials i, i + 256, ..., then a fixed
+// butterfly).  Two barriers: every thread of the workgroup calls it.
+template <bool SC1 = false>
+__device__ __forceinline__ float global_norm(const double* gpart, int64_t npart,
+                                             bool active = true) {
     __shared__ double gn_red[4];
     __shared__ float gn_sh;
-    // up to 8 partials per thread loaded together (fixed summation order)
-    double t = 0.0;
-    for (int64_t i0 = threadIdx.x; i0 < npart; i0 += 8 * 256) {
-        double v[8];
+    if (active) {
+        // up to 8 partials per thread loaded together (fixed summation order)
+        double t = 0.0;
+        for (int64_t i0 = threadIdx.x; i0 < npart; i0 += 8 * 256) {
+            double v[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) {
-            const int64_t i = i0 + (int64_t)u * 256;
-            v[u] = i < npart ? gpart[i] : 0.0;
+            for (int u = 0; u < 8; ++u) {
+                const int64_t i = i0 + (int64_t)u * 256;
+                v[u] = i < npart ? ld_part<SC1>(gpart + i) : 0.0;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u) t += v[u];
         }
-#pragma unroll
-        for (int u = 0; u < 8; ++u) t += v[u];
+        t = wave_sum64d(t);
+        if ((threadIdx.x & 63) == 0) gn_red[threadIdx.x >> 6] = t;
     }
-    t = wave_sum64d(t);
-    if ((threadIdx.x & 63) == 0) gn_red[threadIdx.x >> 6] = t;
     __syncthreads();
     if (threadIdx.x == 0)
         gn_sh = sqrtf((float)((gn_red[0] + gn_red[1]) + (gn_red[2] + gn_red[3])));  // f32 norm
@@ -126,22 +184,56 @@ __device__ inline float global_norm(const double* gpart, int64_t npart) {
 }
 
 // clip_by_global_norm + one Adam step of one parameter (optax 0.1.9
-// scale_by_adam with bias correction).  Contraction off: one rounding per
-// operation as written, so every kernel that calls this (adam_kernel,
-// optim_fused_kernel) produces the same bits whatever the compiler's
-// vectorisation of the caller (an fma's choice of which product to keep
-// unrounded otherwise differs between the two kernels' schedules).
-__device__ __forceinline__ float adam_param(float g, float m_old, float v_old, float q_old, float gn,
-                                            float max_norm, float b1, float b2, float eps, float lr,
-                                            int count, float& mm, float& vv) {
+// scale_by_adam with bias correction); gn is the global norm, count the step
+// being taken.  Contraction off (see the top of the file).
+struct AdamK {
+    float gn, max_norm, b1, b2, eps, lr;
+    int count;
+};
+__device__ __forceinline__ float adam_param(float g, float m_old, float v_old, float q_old,
+                                            const AdamK& a, float& mm, float& vv) {
 #pragma clang fp contract(off)
-    if (!(gn < max_norm)) g = (g / gn) * max_norm;  // clip_by_global_norm
-    mm = (1.f - b1) * g + b1 * m_old;
-    vv = (1.f - b2) * (g * g) + b2 * v_old;
-    const float mhat = mm / (1.f - powf(b1, (float)count));
-    const float vhat = vv / (1.f - powf(b2, (float)count));
-    const float u = mhat / (sqrtf(vhat) + eps);
-    return q_old + (-lr) * u;
+    if (!(a.gn < a.max_norm)) g = (g / a.gn) * a.max_norm;  // clip_by_global_norm
+    mm = (1.f - a.b1) * g + a.b1 * m_old;
+    vv = (1.f - a.b2) * (g * g) + a.b2 * v_old;
+    const float mhat = mm / (1.f - powf(a.b1, (float)a.count));
+    const float vhat = vv / (1.f - powf(a.b2, (float)a.count));
+    const float u = mhat / (sqrtf(vhat) + a.eps);
+    return q_old + (-a.lr) * u;
+}
+
+// Parameter p's update in place (q, m, v); false (nothing changed) where p is
+// no parameter: past the end, or alignment padding.
+__device__ __forceinline__ bool adam_update(const LayoutK& Lk, int64_t p, float g, float& q,
+                                            float& m, float& v, const AdamK& a) {
+    if (p >= Lk.total || is_padding(Lk, p)) return false;
+    q = adam_param(g, m, v, q, a, m, v);
+    return true;
+}
+
+// Adds q^2 of the wave's updated (`live`) parameters p to the wave's row of a
+// block's per-slot sums (a wave's 64 parameters span at most two slots: skip
+// the absent ones).  Contraction off (see the top of the file).
+__device__ __forceinline__ void slot_accumulate(float (&sh)[4][kMaxSlots], int nslot,
+                                                const LayoutK& Lk, int64_t p, bool live, float q) {
+#pragma clang fp contract(off)
+    int slot = -2;
+    float contrib = 0.f;
+    if (live) {
+        slot = proj_slot(Lk, p);
+        contrib = q * q;
+    }
+    for (int s = 0; s < nslot; ++s) {
+        if (!__any(slot == s)) continue;
+        float x = slot == s ? contrib : 0.f;
+        x = wave_sum64(x);
+        if ((threadIdx.x & 63) == 0) sh[(threadIdx.x >> 6) & 3][s] += x;
+    }
+}
+
+// a block's partial of slot s from its four waves' rows
+__device__ __forceinline__ double slot_partial(const float (&sh)[4][kMaxSlots], int s) {
+    return ((double)sh[0][s] + sh[1][s]) + ((double)sh[2][s] + sh[3][s]);
 }
 
 template <int PRE>
@@ -151,12 +243,10 @@ __global__ __launch_bounds__(256) void adam_kernel(LayoutK Lk, float* __restrict
                                                    const int32_t* step, const double* gpart,
                                                    int64_t npart, float lr, float b1, float b2, float eps,
                                                    float max_norm, double* proj_part) {
-#pragma clang fp contract(off)  // (one rounding per operation: optim_fused_kernel's bits)
     // grid-stride over the parameters with at most kAdamBlocks blocks, so the
     // projection reduces a short, fixed list of per-block partials
     __shared__ float sh[4][kMaxSlots];
     const int nslot = 2 * Lk.L + (Lk.lstm_H ? 8 : 0);
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (threadIdx.x < 4 * kMaxSlots) sh[threadIdx.x / kMaxSlots][threadIdx.x % kMaxSlots] = 0.f;
     // this thread's first PRE parameters (grid-stride) are in flight while
     // the global norm is reduced: the headline MLP has one per thread, the
@@ -179,30 +269,16 @@ __global__ __launch_bounds__(256) void adam_kernel(LayoutK Lk, float* __restrict
         }
     }
     const int count = step[0] + 1;
-    const float gn = global_norm(gpart, npart);  // (its barriers also order the sh zeroing)
-    auto update = [&](int64_t p, float g, float m_old, float v_old, float q_old) {
-        float contrib = 0.f;
-        int slot = -2;
-        // (recurrent layouts: the alignment padding before the LSTM segment is not a parameter)
-        const bool pad = Lk.lstm_H && p >= Lk.mlp_total && p < Lk.lstm_off;
-        if (p < Lk.total && !pad) {
-            float mm, vv;
-            const float np = adam_param(g, m_old, v_old, q_old, gn, max_norm, b1, b2, eps, lr,
-                                        count, mm, vv);
+    // (global_norm's barriers also order the sh zeroing)
+    const AdamK a{global_norm(gpart, npart), max_norm, b1, b2, eps, lr, count};
+    auto update = [&](int64_t p, float g, float mm, float vv, float q) {
+        const bool live = adam_update(Lk, p, g, q, mm, vv, a);
+        if (live) {  // (stored at once: the stores land under the slot sums)
             m[p] = mm;
             v[p] = vv;
-            params[p] = np;
-            slot = proj_slot(Lk, p);
-            contrib = np * np;
+            params[p] = q;
         }
-        // per-block partial sums of squares per projection slot (a wave's 64
-        // parameters span at most two slots: skip the absent ones)
-        for (int s = 0; s < nslot; ++s) {
-            if (!__any(slot == s)) continue;
-            float x = slot == s ? contrib : 0.f;
-            x = wave_sum64(x);
-            if (lane == 0) sh[w][s] += x;
-        }
+        slot_accumulate(sh, nslot, Lk, p, live, q);
     };
 #pragma unroll
     for (int u = 0; u < kAdamPre; ++u) {
@@ -215,11 +291,8 @@ __global__ __launch_bounds__(256) void adam_kernel(LayoutK Lk, float* __restrict
         update(p, in ? grads[p] : 0.f, in ? m[p] : 0.f, in ? v[p] : 0.f, in ? params[p] : 0.f);
     }
     __syncthreads();
-    if (threadIdx.x < nslot) {
-        int s = threadIdx.x;
-        proj_part[blockIdx.x * (int64_t)nslot + s] =
-            ((double)sh[0][s] + sh[1][s]) + ((double)sh[2][s] + sh[3][s]);
-    }
+    if (threadIdx.x < nslot)
+        proj_part[blockIdx.x * (int64_t)nslot + threadIdx.x] = slot_partial(sh, threadIdx.x);
 }
 
 template <typename T>
@@ -266,69 +339,81 @@ __device__ inline void write_copies(const LayoutK& Lk, const CopiesK& C, int64_t
     }
 }
 
+// Per-slot sums of squares of the updated tensors (ppo.py:303-338) from the
+// nblk blocks' partials, the same fixed-order tree in every block; NS = 2 L
+// (+ 8 recurrent) slots: the launch picks the instantiation.  Returns the NS
+// totals (LDS).  Two barriers: every thread of the workgroup calls it.
+template <int NS, bool SC1>
+__device__ __forceinline__ const float* slot_totals(const double* ppart, int nblk, bool active) {
+    __shared__ double red[4][kMaxSlots];
+    __shared__ float sq[kMaxSlots];
+    if (active) {
+        // every slot's partials of this thread (blocks tid, tid + 256, ...)
+        // loaded together, then summed per slot in block order (one loop per
+        // slot would wait for each load before issuing the next)
+        double t[NS];
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) t[sl] = 0;
+        for (int b0 = threadIdx.x; b0 < nblk; b0 += 512) {
+            double x[2][NS];
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int sl = 0; sl < NS; ++sl) {
+                    const int b = b0 + 256 * u;
+                    x[u][sl] = b < nblk ? ld_part<SC1>(ppart + (int64_t)b * NS + sl) : 0.0;
+                }
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int sl = 0; sl < NS; ++sl)
+                    if (b0 + 256 * u < nblk) t[sl] += x[u][sl];
+        }
+#pragma unroll
+        for (int sl = 0; sl < NS; ++sl) {
+            const double tt = wave_sum64d(t[sl]);
+            if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][sl] = tt;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < NS) {
+        const int sl = threadIdx.x;
+        sq[sl] = (float)(((red[0][sl] + red[1][sl]) + red[2][sl]) + red[3][sl]);
+    }
+    __syncthreads();
+    return sq;
+}
+
+// val, a parameter of projection slot `slot` (proj_slot), after the projection
+// with the slots' totals sq
+__device__ __forceinline__ float project_value(const LayoutK& Lk, int slot, float val,
+                                               const float* sq, const float* init_norms,
+                                               int norm_params, int norm_ln) {
+    if (slot >= 2 * Lk.L) {  // LSTM gate kernel (ppo.py:303-310 on each ii..ho kernel)
+        if (norm_params) val = (init_norms[Lk.L + slot - 2 * Lk.L] * val) / sqrtf(sq[slot]);
+    } else if (slot >= 0) {
+        if ((slot & 1) == 0) {
+            if (norm_params) val = (init_norms[slot >> 1] * val) / sqrtf(sq[slot]);  // ppo.py:307
+        } else if (norm_ln) {
+            val = sqrtf((float)Lk.H / sq[slot]) * val;  // sqrt(F / (b.b + s.s)) (ppo.py:324-325)
+        }
+    }
+    return val;
+}
+
 template <typename T, int NS>
 __global__ __launch_bounds__(256) void project_kernel(LayoutK Lk, CopiesK C, float* params,
                                                       const float* init_norms, const double* ppart,
                                                       int nblk, int norm_params, int norm_ln,
                                                       int32_t* step) {
-#pragma clang fp contract(off)  // (one rounding per operation: optim_fused_kernel's bits)
-    // per-slot sums of squares of the updated tensors (ppo.py:303-338), the
-    // same fixed-order tree in every block
-    __shared__ double red[4][kMaxSlots];
-    __shared__ float sq[kMaxSlots];
-    constexpr int nslot = NS;  // = 2 L (+ 8 recurrent): the launch picks the instantiation
     const int64_t p = blockIdx.x * (int64_t)256 + threadIdx.x;
     const float val0 = p < Lk.total ? params[p] : 0.f;  // in flight under the slot reduction
-    // every slot's partials of this thread (blocks tid, tid + 256, ...) loaded
-    // together, then summed per slot in block order (one loop per slot would
-    // wait for each load before issuing the next)
-    double t[NS];
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) t[sl] = 0;
-    for (int b0 = threadIdx.x; b0 < nblk; b0 += 512) {
-        double x[2][NS];
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl) {
-                const int b = b0 + 256 * u;
-                x[u][sl] = (b < nblk && sl < nslot) ? ppart[(int64_t)b * nslot + sl] : 0.0;
-            }
-#pragma unroll
-        for (int u = 0; u < 2; ++u)
-#pragma unroll
-            for (int sl = 0; sl < NS; ++sl)
-                if (b0 + 256 * u < nblk && sl < nslot) t[sl] += x[u][sl];
-    }
-#pragma unroll
-    for (int sl = 0; sl < NS; ++sl) {
-        if (sl >= nslot) break;
-        const double tt = wave_sum64d(t[sl]);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][sl] = tt;
-    }
-    __syncthreads();
-    if (threadIdx.x < nslot) {
-        const int sl = threadIdx.x;
-        sq[sl] = (float)(((red[0][sl] + red[1][sl]) + red[2][sl]) + red[3][sl]);
-    }
-    __syncthreads();
+    const float* sq = slot_totals<NS, false>(ppart, nblk, true);
     if (p == 0 && step) step[0] += 1;
     if (p >= Lk.total) return;
-    float val = val0;
     const int slot = proj_slot(Lk, p);
-    if (slot >= 2 * Lk.L) {  // LSTM gate kernel (ppo.py:303-310 on each ii..ho kernel)
-        if (norm_params) val = (init_norms[Lk.L + slot - 2 * Lk.L] * val) / sqrtf(sq[slot]);
-        params[p] = val;
-    } else if (slot >= 0) {
-        const int l = slot >> 1;
-        if ((slot & 1) == 0) {
-            if (norm_params) val = (init_norms[l] * val) / sqrtf(sq[slot]);  // ppo.py:307
-        } else if (norm_ln) {
-            // sqrt(F / (b.b + s.s)) (ppo.py:324-325)
-            val = sqrtf((float)Lk.H / sq[slot]) * val;
-        }
-        params[p] = val;
-    }
+    const float val = project_value(Lk, slot, val0, sq, init_norms, norm_params, norm_ln);
+    if (slot >= 0) params[p] = val;
     write_copies<T>(Lk, C, p, val);
 }
 
@@ -343,9 +428,9 @@ __global__ __launch_bounds__(256) void project_kernel(LayoutK Lk, CopiesK C, flo
 // Bit-identical to the split chain: a workgroup of 256 * VB threads runs VB
 // "virtual" adam_kernel blocks (virtual block vb = VB * blockIdx + tid / 256,
 // the same grid-stride parameter mapping over ablk virtual blocks), writes
-// the same per-(virtual block, slot) partials, and its first 256 threads
-// replay global_norm / sumsq_partial_kernel / project_kernel's reductions in
-// their fixed orders.
+// the same per-(virtual block, slot) partials, and its first 256 threads are
+// the `active` ones of the split kernels' reductions (sumsq_block,
+// global_norm, slot_totals).
 //
 // Hand-off protocol (MI355X_MICROARCH.md, hand-off table row 1, "one lane of
 // each storing workgroup ... agent-scope atomic add"): partials are stored
@@ -370,17 +455,6 @@ struct GridBarK {
     uint64_t* base;
     uint64_t* fail;
 };
-
-__device__ inline uint64_t ld_sc1(const uint64_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-__device__ inline double ld_sc1d(const double* p) {
-    return __builtin_bit_cast(double, ld_sc1((const uint64_t*)p));
-}
-__device__ inline void st_sc1d(double* p, double x) {
-    __hip_atomic_store((uint64_t*)p, __builtin_bit_cast(uint64_t, x), __ATOMIC_RELAXED,
-                       __HIP_MEMORY_SCOPE_AGENT);
-}
 
 // Arrive and wait until `target` arrivals have been counted.  Every thread
 // of the workgroup calls it (its sc1 partial stores issued before).
@@ -412,17 +486,12 @@ __global__ __launch_bounds__(256 * VB) void optim_fused_kernel(
     int32_t* step, const double* gpart_in, int64_t npart_in, double* gpart, double* ppart, int ablk,
     float lr, float b1, float b2, float eps, float max_norm, int norm_params, int norm_ln,
     GridBarK gb) {
-#pragma clang fp contract(off)  // (one rounding per operation: the split kernels' bits)
     extern __shared__ char fused_dyn[];  // (unused: sized so that one workgroup fits per CU)
     __shared__ float sh[VB][4][kMaxSlots];
-    __shared__ double red[4][kMaxSlots];
-    __shared__ float sq[kMaxSlots];
-    __shared__ double gn_red[4];
-    __shared__ float gn_sh;
     __shared__ uint64_t base_sh;
-    constexpr int nslot = NS;
-    const int tid = threadIdx.x, vt = tid & 255, half = tid >> 8, w = vt >> 6, lane = tid & 63;
+    const int tid = threadIdx.x, vt = tid & 255, half = tid >> 8;
     const int vb = VB * blockIdx.x + half;
+    const bool first = tid < 256;  // the threads that reduce; EVERY thread calls each stage
     const uint64_t G = gridDim.x;
     for (int i = tid; i < VB * 4 * kMaxSlots; i += 256 * VB) (&sh[0][0][0])[i] = 0.f;
     if (tid == 0) base_sh = ld_sc1(gb.base);
@@ -454,116 +523,31 @@ __global__ __launch_bounds__(256 * VB) void optim_fused_kernel(
     if (NORM) {
         // sumsq_partial_kernel's kNormBlocks partials of grads^2 (the
         // all-reduced gradient), virtual norm block k on the first 256 threads
-        for (int k = blockIdx.x; k < kNormBlocks; k += gridDim.x) {
-            double s = 0;
-            if (tid < 256) {
-                const int64_t st = (int64_t)kNormBlocks * 256;
-                for (int64_t i0 = k * 256 + tid; i0 < Lk.total; i0 += 8 * st) {
-                    float x[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) x[u] = i0 + u * st < Lk.total ? grads[i0 + u * st] : 0.f;
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (i0 + u * st < Lk.total) {
-                            const double d = x[u];
-                            s += d * d;
-                        }
-                }
-                s = wave_sum64d(s);
-                if (lane == 0) gn_red[w] = s;
-            }
-            __syncthreads();
-            if (tid == 0) st_sc1d(gpart + k, ((gn_red[0] + gn_red[1]) + gn_red[2]) + gn_red[3]);
+        for (int k = blockIdx.x; k < kNormBlocks; k += gridDim.x) {  // (block-uniform)
+            sumsq_block<true>(grads, Lk.total, k, kNormBlocks, first, gpart);
             __syncthreads();
         }
         grid_sync(gb, base + (uint64_t)(++nbar) * G);
         gp = gpart;
         np = kNormBlocks;
     }
-    // global_norm's fixed order on the first 256 threads (sc1 loads where
-    // the partials came from this launch)
-    if (tid < 256) {
-        double t = 0.0;
-        for (int64_t i0 = tid; i0 < np; i0 += 8 * 256) {
-            double x[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int64_t i = i0 + (int64_t)u * 256;
-                x[u] = i < np ? (NORM ? ld_sc1d(gp + i) : gp[i]) : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) t += x[u];
-        }
-        t = wave_sum64d(t);
-        if (lane == 0) gn_red[w] = t;
-    }
-    __syncthreads();
-    if (tid == 0) gn_sh = sqrtf((float)((gn_red[0] + gn_red[1]) + (gn_red[2] + gn_red[3])));
-    __syncthreads();
-    const float gn = gn_sh;
+    // (sc1 loads where the partials came from this launch)
+    const AdamK a{global_norm<NORM>(gp, np, first), max_norm, b1, b2, eps, lr, count};
 
-    // clip + Adam (adam_kernel's arithmetic); the new values and moments stay
-    // in registers until after the barrier, so the barrier's vmcnt(0) waits
-    // for the partials' stores only
-    float nq[PRE];
+    // clip + Adam; the new values and moments stay in registers until after
+    // the barrier, so the barrier's vmcnt(0) waits for the partials' stores only
 #pragma unroll
     for (int u = 0; u < PRE; ++u) {
         const int64_t p = p0 + u * stride;
-        nq[u] = qq[u];
         if (vb >= ablk || p - vt >= Lk.total) continue;  // (uniform per virtual block)
-        float contrib = 0.f;
-        int slot = -2;
-        const bool pad = Lk.lstm_H && p >= Lk.mlp_total && p < Lk.lstm_off;
-        if (p < Lk.total && !pad) {
-            nq[u] = adam_param(gq[u], mq[u], vq[u], qq[u], gn, max_norm, b1, b2, eps, lr, count,
-                               mq[u], vq[u]);
-            slot = proj_slot(Lk, p);
-            contrib = nq[u] * nq[u];
-        }
-        for (int s2 = 0; s2 < nslot; ++s2) {
-            if (!__any(slot == s2)) continue;
-            float x = slot == s2 ? contrib : 0.f;
-            x = wave_sum64(x);
-            if (lane == 0) sh[half][w][s2] += x;
-        }
+        const bool live = adam_update(Lk, p, gq[u], qq[u], mq[u], vq[u], a);
+        slot_accumulate(sh[half], NS, Lk, p, live, qq[u]);
     }
     __syncthreads();
-    if (vt < nslot && vb < ablk) {
-        const int s2 = vt;
-        st_sc1d(ppart + vb * (int64_t)nslot + s2,
-                ((double)sh[half][0][s2] + sh[half][1][s2]) + ((double)sh[half][2][s2] + sh[half][3][s2]));
-    }
+    if (vt < NS && vb < ablk) st_sc1d(ppart + vb * (int64_t)NS + vt, slot_partial(sh[half], vt));
     grid_sync(gb, base + (uint64_t)(++nbar) * G);
 
-    // project_kernel's per-slot totals (fixed order, first 256 threads)
-    if (tid < 256) {
-        double t[NS];
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) t[sl] = 0;
-        for (int b0 = tid; b0 < ablk; b0 += 512) {
-            double x[2][NS];
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl) {
-                    const int b = b0 + 256 * u;
-                    x[u][sl] = b < ablk ? ld_sc1d(ppart + (int64_t)b * nslot + sl) : 0.0;
-                }
-#pragma unroll
-            for (int u = 0; u < 2; ++u)
-#pragma unroll
-                for (int sl = 0; sl < NS; ++sl)
-                    if (b0 + 256 * u < ablk) t[sl] += x[u][sl];
-        }
-#pragma unroll
-        for (int sl = 0; sl < NS; ++sl) {
-            const double tt = wave_sum64d(t[sl]);
-            if (lane == 0) red[w][sl] = tt;
-        }
-    }
-    __syncthreads();
-    if (tid < nslot) sq[tid] = (float)(((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid]);
-    __syncthreads();
+    const float* sq = slot_totals<NS, true>(ppart, ablk, first);
     if (blockIdx.x == 0 && tid == 0) {
         if (step) step[0] += 1;
         // arrivals so far, for the next launch's targets (every workgroup has
@@ -571,24 +555,14 @@ __global__ __launch_bounds__(256 * VB) void optim_fused_kernel(
         __hip_atomic_store(gb.base, base + (uint64_t)nbar * G, __ATOMIC_RELAXED,
                            __HIP_MEMORY_SCOPE_AGENT);
     }
-    // projection (project_kernel's arithmetic) + master params + images
+    // projection + master params + images
 #pragma unroll
     for (int u = 0; u < PRE; ++u) {
         const int64_t p = p0 + u * stride;
         if (vb >= ablk || p >= Lk.total) continue;
-        const bool pad = Lk.lstm_H && p >= Lk.mlp_total && p < Lk.lstm_off;
-        float val = nq[u];
-        const int slot = proj_slot(Lk, p);
-        if (slot >= 2 * Lk.L) {
-            if (norm_params) val = (init_norms[Lk.L + slot - 2 * Lk.L] * val) / sqrtf(sq[slot]);
-        } else if (slot >= 0) {
-            const int l = slot >> 1;
-            if ((slot & 1) == 0) {
-                if (norm_params) val = (init_norms[l] * val) / sqrtf(sq[slot]);
-            } else if (norm_ln) {
-                val = sqrtf((float)Lk.H / sq[slot]) * val;
-            }
-        }
+        const bool pad = is_padding(Lk, p);
+        const float val = project_value(Lk, proj_slot(Lk, p), qq[u], sq, init_norms, norm_params,
+                                        norm_ln);
         if (!pad) {
             params[p] = val;
             m[p] = mq[u];
@@ -644,7 +618,10 @@ static void launch_project(int nslot, dim3 grid, hipStream_t s, const LayoutK& L
 
 // ---------------------------------------------------------------------------
 // Flat optimizer (mlearn_flat_optim_step): any policy tree's f32 parameter
-// vector with a table of projection groups.
+// vector with a table of projection groups.  flat_adam_kernel does not call
+// adam_param: its lines are not under contract(off) (the compiler fuses
+// q + (-lr) u into one fma) and hoist 1 - b^t, and the shared call moved the
+// parameters' last bit in every case of tests/test_gpu_optim_bits.py.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void flat_adam_kernel(float* __restrict__ params,
                                                         const float* __restrict__ grads,
