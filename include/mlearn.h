@@ -787,6 +787,57 @@ int mlearn_continuous_stats_bwd(const void* means, int64_t ld_means, const void*
                                 void* d_stds, int64_t ld_ds, mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* HL-Gauss heads (models.py:177-250 HLGaussDist, 309-321                  */
+/* HLGaussTwoPartDist); the torch path's critic statistics (additive       */
+/* exports)                                                                */
+/* ---------------------------------------------------------------------- */
+/* num_parts 1: one HLGaussDist.  num_parts 2: HLGaussTwoPartDist, part 0 the
+ * small head and part 1 the large head; the value is the sum of the parts'
+ * means and the loss the sum of their losses, the target t split in the kernel
+ * as small = fmodf(t, 2), large = t - small (both exact in f32).  Per part:
+ * num_bins odd within 3..255, device pointers centers[num_bins] and
+ * bounds[num_bins + 1] (f32); each part clips its target to [centers[0],
+ * centers[num_bins - 1]].  Logits: per part [R][num_bins] in `dtype` (f32 or
+ * bf16, upcast to f32) with a row stride ld >= num_bins in elements, any base
+ * alignment (the parts may be column ranges of one wider tensor); logits1 /
+ * ld1 (and d_logits1 / ld_d1) are not read with one part.  targets, loss, mean
+ * and the incoming gradients are contiguous f32 [R].  Bad arguments (num_parts
+ * outside {1, 2}, a bin count that is even or outside 3..255, a null required
+ * pointer, ld below the bin count, another dtype, R < 0) are MLEARN_EINVAL
+ * before any pointer is followed or the device is touched; R == 0 succeeds and
+ * launches nothing.  One launch each on `stream`, nothing allocated, no host
+ * synchronisation, no atomics; every output element has one writer and a row's
+ * results do not depend on R or on the other rows. */
+typedef struct mlearn_hlgauss_tables {
+    int32_t num_parts;
+    int32_t num_bins[2];
+    float smoothness;
+    const float* centers[2];
+    const float* bounds[2];
+} mlearn_hlgauss_tables;
+
+/* mean(): per part the middle bin plus the mirrored pairs (exactly 0 at zero
+ * logits over antisymmetric centres); two parts: mean_small + mean_large. */
+int mlearn_hlgauss_mean(const mlearn_hlgauss_tables* tables, const void* logits0, int64_t ld0,
+                        const void* logits1, int64_t ld1, int32_t dtype, int64_t R, float* mean,
+                        mlearn_stream_t stream);
+/* loss(targets) and, where mean is not NULL, mean() of the same logits. */
+int mlearn_hlgauss_loss(const mlearn_hlgauss_tables* tables, const void* logits0, int64_t ld0,
+                        const void* logits1, int64_t ld1, int32_t dtype, const float* targets,
+                        int64_t R, float* loss, float* mean, mlearn_stream_t stream);
+/* Their gradient, recomputed from the logits and targets (the forward saves
+ * nothing else): per part, with p = softmax(logits) and c the smoothed target,
+ *   d_j = g_loss (sum(c) p_j - c_j) + g_mean p_j (centers_j - mean_part).
+ * g_loss / g_mean may be NULL (zero).  d_logits in `dtype` with row strides
+ * ld_d >= num_bins, each element rounded once; columns past num_bins are not
+ * written. */
+int mlearn_hlgauss_loss_bwd(const mlearn_hlgauss_tables* tables, const void* logits0, int64_t ld0,
+                            const void* logits1, int64_t ld1, int32_t dtype, const float* targets,
+                            const float* g_loss, const float* g_mean, void* d_logits0,
+                            int64_t ld_d0, void* d_logits1, int64_t ld_d1, int64_t R,
+                            mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Synthetic dummy vec-env (test/bench sim plugin, not part of the         */
 /* reference: stands in for the Madrona sim_fns['step'] custom call,       */
 /* rollouts.py:905-936).                                                   */

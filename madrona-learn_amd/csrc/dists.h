@@ -142,6 +142,13 @@ __device__ inline float twohot_mean_g(const float* lg, int nb, const float* bins
     return (__expf(lg[mid] - mx) / se) * bins[mid] + acc;
 }
 
+// d mean() / d logit_j = p_j (bins_j - mean), from twohot_mean_g's mean, mx
+// and se over the same logits (csrc/hlgauss.hip: the g_mean term).
+__device__ inline float mean_dlogit(const float* lg, const float* bins, int j, float mx, float se,
+                                    float mean) {
+    return (__expf(lg[j] - mx) / se) * (bins[j] - mean);
+}
+
 // Every lane returns the loss and mean(); each lane writes the scaled
 // d loss / d logit of its own bins.
 template <int G>

@@ -38,6 +38,11 @@ class ContinuousLayout(Structure):  # mlearn_continuous_layout
                 ("std_min", c_float * MAX_GROUPS), ("std_max", c_float * MAX_GROUPS)]
 
 
+class HLGaussTables(Structure):  # mlearn_hlgauss_tables
+    _fields_ = [("num_parts", c_int32), ("num_bins", c_int32 * 2), ("smoothness", c_float),
+                ("centers", c_void_p * 2), ("bounds", c_void_p * 2)]
+
+
 class MlpPolicy(Structure):
     _fields_ = [("dtype", c_int32), ("obs_dim", c_int32), ("hidden", c_int32),
                 ("num_layers", c_int32), ("critic_bins", c_int32), ("actions", ActionLayout),
@@ -267,6 +272,13 @@ _SIGNATURES = {
                                           c_int64, _P, _P, _P, _S]),
     "mlearn_continuous_stats_bwd": (c_int32, [_P, c_int64, _P, c_int64, c_int32, ContinuousLayout,
                                               c_int64, _P, _P, _P, _P, c_int64, _P, c_int64, _S]),
+    "mlearn_hlgauss_mean": (c_int32, [POINTER(HLGaussTables), _P, c_int64, _P, c_int64, c_int32,
+                                      c_int64, _P, _S]),
+    "mlearn_hlgauss_loss": (c_int32, [POINTER(HLGaussTables), _P, c_int64, _P, c_int64, c_int32,
+                                      _P, c_int64, _P, _P, _S]),
+    "mlearn_hlgauss_loss_bwd": (c_int32, [POINTER(HLGaussTables), _P, c_int64, _P, c_int64,
+                                          c_int32, _P, _P, _P, _P, c_int64, _P, c_int64, c_int64,
+                                          _S]),
     "mlearn_dummy_env_step": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_uint32, c_uint32,
                                         c_uint32, _P, _P, _P, _S]),
     "mlearn_dummy_env_reset": (c_int32, [_P, c_int64, c_int32, c_uint32, c_uint32, c_uint32, _P,

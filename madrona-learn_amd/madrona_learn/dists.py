@@ -6,6 +6,7 @@ the GPU) and dispatches to the HIP kernels.  RNG: the reference's
 DESIGN.md "RNG".
 """
 
+import ctypes
 import math
 
 import torch
@@ -294,18 +295,156 @@ class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
         return SymExpTwoHotDistribution(self.logits.reshape(*shape, self.logits.shape[-1]))
 
 
+def _hl_tables(parts):
+    """mlearn_hlgauss_tables of one or two HLGaussDist (their table tensors
+    stay alive through the dists)."""
+    t = nat.HLGaussTables()
+    t.num_parts = len(parts)
+    for p, d in enumerate(parts):
+        t.num_bins[p] = int(d.centers.shape[-1])
+        t.centers[p], t.bounds[p] = d.centers.data_ptr(), d.bounds.data_ptr()
+    t.smoothness = parts[0].smoothness
+    return t
+
+
+def _hl_rows(parts, detach=False):
+    """Each part's raw logits as a [R, nb] view with unit column stride (a
+    copy only where no such view exists), all in one dtype the kernels read."""
+    xs = [d._raw.detach() if detach else d._raw for d in parts]
+    if any(x.dtype != xs[0].dtype for x in xs) or \
+            xs[0].dtype not in (torch.float32, torch.bfloat16):
+        xs = [x.float() for x in xs]
+    out = []
+    for x in xs:
+        nb = x.shape[-1]
+        x = x.reshape(-1, nb)
+        if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < nb):
+            x = x.contiguous()
+        out.append(x)
+    return out
+
+
+def _hl_args(tables, lgs):
+    """The leading arguments of the three entry points: tables, then
+    (pointer, row stride) of each part (the second part's unused with one)."""
+    a = [ctypes.byref(tables)]
+    for x in lgs:
+        a += [x.data_ptr(), x.stride(0) if x.shape[0] > 1 else x.shape[1]]
+    if len(lgs) == 1:
+        a += [None, 0]
+    return a + [nat.dtype_code(lgs[0].dtype)]
+
+
+def _hl_mean(parts):
+    """mean() of one or two parts on mlearn_hlgauss_mean, [R] f32 (no
+    gradient: the rollout's and the bootstrap's value)."""
+    lgs = _hl_rows(parts, detach=True)
+    R = lgs[0].shape[0]
+    mean = torch.empty(R, dtype=torch.float32, device=lgs[0].device)
+    if R:
+        nat.check(nat.lib().mlearn_hlgauss_mean(*_hl_args(_hl_tables(parts), lgs), R,
+                                                nat.ptr(mean), nat.stream_handle()),
+                  "hlgauss_mean")
+    return mean
+
+
+class _HLGaussLoss(torch.autograd.Function):
+    """loss_and_mean of one or two HL-Gauss parts on mlearn_hlgauss_loss, the
+    gradient on mlearn_hlgauss_loss_bwd (recomputed from the logits and the
+    targets: nothing else is saved).  logits: [R, nb] views with unit column
+    stride, one per part."""
+
+    @staticmethod
+    def forward(ctx, targets, parts, *logits):
+        R = logits[0].shape[0]
+        dev = logits[0].device
+        tgt = targets.to(torch.float32).reshape(R).contiguous()
+        loss = torch.empty(R, dtype=torch.float32, device=dev)
+        mean = torch.empty_like(loss)
+        tables = _hl_tables(parts)
+        if R:
+            nat.check(nat.lib().mlearn_hlgauss_loss(
+                *_hl_args(tables, logits), nat.ptr(tgt), R, nat.ptr(loss), nat.ptr(mean),
+                nat.stream_handle()), "hlgauss_loss")
+        ctx.save_for_backward(tgt, *logits)
+        ctx.parts = parts
+        ctx.set_materialize_grads(False)
+        return loss, mean
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mean):
+        tgt, *logits = ctx.saved_tensors
+        R = tgt.shape[0]
+        g_loss = None if g_loss is None else g_loss.to(torch.float32).contiguous()
+        g_mean = None if g_mean is None else g_mean.to(torch.float32).contiguous()
+        ds = [torch.empty(x.shape, dtype=x.dtype, device=x.device) for x in logits]
+        dd = [(d.data_ptr(), d.shape[1]) for d in ds] + [(None, 0)] * (2 - len(ds))
+        if R:
+            nat.check(nat.lib().mlearn_hlgauss_loss_bwd(
+                *_hl_args(_hl_tables(ctx.parts), logits), nat.ptr(tgt), nat.ptr(g_loss),
+                nat.ptr(g_mean), dd[0][0], dd[0][1], dd[1][0], dd[1][1], R, nat.stream_handle()),
+                "hlgauss_loss_bwd")
+        return (None, None, *ds)
+
+
+def _hl_use_hip(kernel, ref, who):
+    """kernel: 0 / "hip" / "torch"; ref: a logits tensor.  True: the HIP
+    kernels of csrc/hlgauss.hip; False: the torch composition (kernel="torch",
+    and CPU tensors)."""
+    if kernel == "torch" or not ref.is_cuda:
+        if kernel == "hip":
+            raise NotImplementedError(f"{who}: kernel='hip' needs GPU tensors")
+        return False
+    return True
+
+
+def _hl_loss_and_mean(parts, targets):
+    lead = parts[0]._raw.shape[:-1]
+    loss, mean = _HLGaussLoss.apply(targets, tuple(parts), *_hl_rows(parts))
+    return loss.reshape(*lead, 1), mean.reshape(*lead, 1)
+
+
+def _hl_mean_any(parts):
+    """mean() on the kernels: through _HLGaussLoss where a gradient may be
+    asked for (the torch mean() is differentiable), else the mean kernel."""
+    lead = parts[0]._raw.shape[:-1]
+    if torch.is_grad_enabled() and any(d._raw.requires_grad for d in parts):
+        zeros = torch.zeros(lead, dtype=torch.float32, device=parts[0]._raw.device)
+        return _HLGaussLoss.apply(zeros, tuple(parts), *_hl_rows(parts))[1].reshape(*lead, 1)
+    return _hl_mean(parts).reshape(*lead, 1)
+
+
 class HLGaussDist:  # models.py:177-250 (critic of HLGaussCritic)
     """Categorical critic over linear bins, trained against a Gaussian-smoothed
     target.  The torch path's implementation; the fused kernels compute the
-    same mean() / loss in csrc/dists.h (hlgauss_ce_g)."""
+    same mean() / loss in csrc/dists.h (hlgauss_ce_g).
 
-    def __init__(self, logits, centers, bounds, smoothness):
-        self.logits = logits.float()
-        self.centers = torch.as_tensor(centers, dtype=torch.float32).to(self.logits.device)
-        self.bounds = torch.as_tensor(bounds, dtype=torch.float32).to(self.logits.device)
+    ``kernel``: "torch" (default) evaluates a torch composition of the
+    formulas (also what CPU tensors get); 0 / "hip" run the HIP kernels of
+    csrc/hlgauss.hip on GPU tensors (3..255 bins), which read the logits in
+    their own dtype (f32 / bf16) and row stride."""
+
+    kernel = "torch"  # the default of instances created without kernel=
+
+    def __init__(self, logits, centers, bounds, smoothness, kernel=None):
+        self._raw = logits
+        self._f32 = None
+        self.centers = torch.as_tensor(centers, dtype=torch.float32).to(logits.device)
+        self.bounds = torch.as_tensor(bounds, dtype=torch.float32).to(logits.device)
         self.smoothness = float(smoothness)
+        if kernel is not None:
+            self.kernel = _kernel_choice(kernel)
 
-    def mean(self):
+    @property
+    def logits(self):  # models.py:305 upcasts to f32
+        if self._f32 is None:
+            self._f32 = self._raw.float()
+        return self._f32
+
+    def _hip(self):
+        return _hl_use_hip(self.kernel, self._raw, "HLGaussDist")
+
+    def _mean_torch(self):
         c = self.centers
         mid = (c.shape[-1] - 1) // 2
         p = torch.softmax(self.logits, -1)
@@ -314,7 +453,7 @@ class HLGaussDist:  # models.py:177-250 (critic of HLGaussCritic)
         return (p[..., mid:mid + 1] * c[mid:mid + 1]).sum(-1, keepdim=True) + \
             (lo + hi).sum(-1, keepdim=True)
 
-    def loss(self, targets):
+    def _loss_torch(self, targets):
         b = self.bounds
         nbd = b.shape[-1]
         t = torch.minimum(torch.maximum(targets.float(), self.centers[0]), self.centers[-1])
@@ -328,6 +467,85 @@ class HLGaussDist:  # models.py:177-250 (critic of HLGaussCritic)
         logp = self.logits - torch.logsumexp(self.logits, -1, keepdim=True)
         return -(c * logp).sum(-1, keepdim=True)
 
+    def mean(self):
+        return _hl_mean_any([self]) if self._hip() else self._mean_torch()
+
+    def loss(self, targets):
+        return _hl_loss_and_mean([self], targets)[0] if self._hip() else self._loss_torch(targets)
+
+    def loss_and_mean(self, targets):
+        """(loss(targets), mean()), each [..., 1]: one launch on the kernels."""
+        if self._hip():
+            return _hl_loss_and_mean([self], targets)
+        return self._loss_torch(targets), self._mean_torch()
+
     def reshape(self, *shape):
-        return HLGaussDist(self.logits.reshape(*shape, self.logits.shape[-1]), self.centers,
-                           self.bounds, self.smoothness)
+        return HLGaussDist(self._raw.reshape(*shape, self._raw.shape[-1]), self.centers,
+                           self.bounds, self.smoothness, kernel=self.kernel)
+
+
+class HLGaussTwoPartDist:  # models.py:309-321 (critic of HLGaussTwoPartCritic)
+    """The sum of two HL-Gauss heads: ``small_dist`` over the remainder of the
+    target modulo 2 (sign of the target), ``large_dist`` over the target minus
+    that remainder.
+
+    ``kernel``: 0 (default) / "hip" run mean / loss / gradient as one launch
+    each over both parts (csrc/hlgauss.hip) on GPU tensors; "torch" evaluates
+    the two HLGaussDist compositions (also what CPU tensors get)."""
+
+    kernel = 0  # the default of instances created without kernel=
+
+    def __init__(self, small_dist, large_dist, kernel=None):
+        self.small_dist, self.large_dist = small_dist, large_dist
+        if kernel is not None:
+            self.kernel = _kernel_choice(kernel)
+        if small_dist._raw.shape[:-1] != large_dist._raw.shape[:-1]:
+            raise ValueError(f"HLGaussTwoPartDist: the parts' logits differ in their leading "
+                             f"dimensions, {tuple(small_dist._raw.shape)} and "
+                             f"{tuple(large_dist._raw.shape)}")
+        if small_dist.smoothness != large_dist.smoothness:
+            raise ValueError("HLGaussTwoPartDist: the parts differ in smoothness")
+
+    @property
+    def parts(self):
+        return [self.small_dist, self.large_dist]
+
+    @property
+    def logits(self):
+        """Both heads' logits side by side (small first)."""
+        return torch.cat([self.small_dist.logits, self.large_dist.logits], -1)
+
+    def _hip(self):
+        return _hl_use_hip(self.kernel, self.small_dist._raw, "HLGaussTwoPartDist")
+
+    @staticmethod
+    def split(targets):
+        """(small, large) targets: small = targets mod (sign(targets) 2), C's
+        fmod(t, 2); both exact in f32."""
+        t = targets.float()
+        small = t % (torch.where(t >= 0, 1, -1) * 2)
+        return small, t - small
+
+    def mean(self):
+        if self._hip():
+            return _hl_mean_any(self.parts)
+        return self.small_dist._mean_torch() + self.large_dist._mean_torch()
+
+    def _loss_torch(self, targets):
+        small, large = self.split(targets)
+        return self.small_dist._loss_torch(small) + self.large_dist._loss_torch(large)
+
+    def loss(self, targets):
+        return _hl_loss_and_mean(self.parts, targets)[0] if self._hip() \
+            else self._loss_torch(targets)
+
+    def loss_and_mean(self, targets):
+        """(loss(targets), mean()), each [..., 1]: one launch on the kernels."""
+        if self._hip():
+            return _hl_loss_and_mean(self.parts, targets)
+        return self._loss_torch(targets), \
+            self.small_dist._mean_torch() + self.large_dist._mean_torch()
+
+    def reshape(self, *shape):
+        return HLGaussTwoPartDist(self.small_dist.reshape(*shape), self.large_dist.reshape(*shape),
+                                  kernel=self.kernel)

@@ -57,7 +57,7 @@ import torch
 from torch import nn
 
 from . import _native as nat
-from .dists import (DiscreteActionDistributions, HLGaussDist, PhiloxKey,
+from .dists import (DiscreteActionDistributions, HLGaussDist, HLGaussTwoPartDist, PhiloxKey,
                     SymExpTwoHotDistribution)
 from .dynamic_scale import DynamicScale
 from .models import LayerNorm, _Dense, action_groups, continuous_groups
@@ -68,6 +68,8 @@ from .rnn import MultiLayerLSTMCell
 from .train_state import _ckpt_safe
 from .tree import leaf_pairs, leaves, map_leaves, zip_leaves
 
+_HLGAUSS = (HLGaussDist, HLGaussTwoPartDist)  # the critics trained with hlgauss_critic
+
 
 @dataclass(frozen=True)
 class GenericArch:
@@ -75,7 +77,9 @@ class GenericArch:
     obs_dim: int            # width of the flattened preprocessed observation row
     buckets: tuple
     dtype: torch.dtype      # compute dtype (the store's observation dtype)
-    critic_bins: int = 1    # 1: scalar critic; > 1: SymExpTwoHotDistribution logits
+    # 1: scalar critic; > 1: the logits of a SymExpTwoHotDistribution / HLGaussDist, or of
+    # both heads of an HLGaussTwoPartDist together (254 for HLGaussTwoPartCritic.create)
+    critic_bins: int = 1
     lstm_hidden: int = 0
     # continuous actions: (G, D) of the actor's [..., G, D] head (buckets is
     # then empty); None: discrete buckets
@@ -257,10 +261,10 @@ class TorchPolicyState:
             self.rnn0 = rnn
             out, _ = self.actor_critic.rollout(PhiloxKey(0, 0), rnn, one)
         crit = out["critic"]
-        self.critic_bins = 1 if not isinstance(crit, (SymExpTwoHotDistribution, HLGaussDist)) \
+        self.critic_bins = 1 if not isinstance(crit, (SymExpTwoHotDistribution,) + _HLGAUSS) \
             else int(crit.logits.shape[-1])
         # what the critic returns (train._check_critic_flags)
-        self.critic_form = "hlgauss" if isinstance(crit, HLGaussDist) else \
+        self.critic_form = "hlgauss" if isinstance(crit, _HLGAUSS) else \
             ("two-hot" if self.critic_bins > 1 else "scalar")
         self.codec = ObsCodec(pre)
         # the action kind follows what the actor's head returned: f32 [1, G, D]
@@ -458,8 +462,9 @@ class TorchTrainState:
 
 def _critic_value(crit):
     """_compute_value_estimate (rollouts.py:601-605): the scalar critic, or
-    SymExpTwoHotDistribution.mean() / HLGaussDist.mean()."""
-    if isinstance(crit, (SymExpTwoHotDistribution, HLGaussDist)):
+    SymExpTwoHotDistribution.mean() / HLGaussDist.mean() /
+    HLGaussTwoPartDist.mean()."""
+    if isinstance(crit, (SymExpTwoHotDistribution,) + _HLGAUSS):
         return crit.mean().reshape(-1)
     return crit.float().reshape(-1)
 
@@ -566,8 +571,9 @@ class TorchPPO(PPO):
             # ppo.py:57 asserts not normalize_values for distributional
             # critics: the two-hot loss ignores the normaliser, yet GAE would
             # invert the two-hot mean with drifting estimates
-            raise ValueError("normalize_values with a SymExpTwoHotDistribution / HLGaussDist "
-                             "critic (the reference asserts against it, ppo.py:57)")
+            raise ValueError("normalize_values with a SymExpTwoHotDistribution / HLGaussDist / "
+                             "HLGaussTwoPartDist critic (the reference asserts against it, "
+                             "ppo.py:57)")
         self.groups = action_groups(cfg.actions)
         self.cont = continuous_groups(self.groups)
         if self.cont is not None:
@@ -677,9 +683,9 @@ class TorchPPO(PPO):
         if isinstance(crit, SymExpTwoHotDistribution):
             vl = crit.two_hot_cross_entropy_loss(R.reshape(-1, 1)).reshape(T, M)
             V = crit.mean().reshape(T, M)
-        elif isinstance(crit, HLGaussDist):  # ppo.py:178-185
-            vl = crit.loss(R.reshape(-1, 1)).reshape(T, M)
-            V = crit.mean().reshape(T, M)
+        elif isinstance(crit, _HLGAUSS):  # ppo.py:178-185
+            vl, V = crit.loss_and_mean(R.reshape(-1, 1))
+            vl, V = vl.reshape(T, M), V.reshape(T, M)
         else:
             V = crit.float().reshape(T, M)
             vpred = V

@@ -396,9 +396,11 @@ class HLGaussCritic(nn.Module):  # models.py:253-307 (HLGaussDist head)
     logits) and bounds [num_bins + 1]: f32 arrays, module configuration (not
     trained, not checkpointed)."""
 
-    def __init__(self, dtype, centers, bounds, smoothness=0.75, weight_init=constant(0.0)):
+    def __init__(self, dtype, centers, bounds, smoothness=0.75, weight_init=constant(0.0),
+                 kernel=None):
         super().__init__()
         self.dtype = canonical_dtype(dtype)
+        self.kernel = kernel  # HLGaussDist's switch (None: its default, the torch composition)
         self.centers = np.ascontiguousarray(np.asarray(centers, dtype=np.float32))
         self.bounds = np.ascontiguousarray(np.asarray(bounds, dtype=np.float32))
         if self.centers.ndim != 1 or self.bounds.shape != (self.centers.size + 1,):
@@ -429,4 +431,88 @@ class HLGaussCritic(nn.Module):  # models.py:253-307 (HLGaussDist head)
         if self._tables is None or self._tables[0].device != features.device:
             self._tables = tuple(torch.from_numpy(a).to(features.device)
                                  for a in (self.centers, self.bounds))
-        return HLGaussDist(self.impl(features), *self._tables, self.smoothness)
+        return HLGaussDist(self.impl(features), *self._tables, self.smoothness, kernel=self.kernel)
+
+
+def _hlgauss_table(who, name, centers, bounds):
+    c = np.ascontiguousarray(np.asarray(centers, dtype=np.float32))
+    b = np.ascontiguousarray(np.asarray(bounds, dtype=np.float32))
+    if c.ndim != 1 or c.size < 3 or c.size % 2 != 1:
+        raise ValueError(f"{who}: {name}_centers needs an odd number of bins >= 3 (mean() is the "
+                         f"symmetric sum around the middle one), got shape {c.shape}")
+    if b.shape != (c.size + 1,):
+        raise ValueError(f"{who}: {name}_bounds must hold one more value than {name}_centers, "
+                         f"got {c.shape} centers and {b.shape} bounds")
+    if not (np.diff(b) > 0).all():
+        raise ValueError(f"{who}: {name}_bounds must be strictly increasing")
+    return c, b
+
+
+def _floating_point_bins(mantissa_bits, exp_bits, bias):
+    """gen_floating_point_bins (models.py:344-378) with denormals: the centres
+    are the non-negative values of a sign / exp_bits / mantissa_bits float
+    format of that bias, mirrored around 0; each bound lies half a spacing of
+    its exponent below its centre (f32 arithmetic, as the reference's)."""
+    steps = 2 ** mantissa_bits
+    half, widths = [], []
+    for e in range(2 ** exp_bits):
+        scale = 2.0 ** ((1 if e == 0 else e) - bias)
+        for m in range(steps):
+            half.append((m / steps if e == 0 else 1 + m / steps) * scale)
+            widths.append(scale / steps)
+    half = np.asarray(half, dtype=np.float32)
+    widths = np.asarray(widths, dtype=np.float32)
+    centers = np.concatenate([-half[:0:-1], half])
+    widths = np.concatenate([widths[:0:-1], widths])
+    bounds = centers - np.float32(0.5) * widths
+    bounds = np.concatenate([bounds, [bounds[-1] + widths[-1]]])
+    return centers.astype(np.float32), bounds.astype(np.float32)
+
+
+class HLGaussTwoPartCritic(nn.Module):  # models.py:324-447 (HLGaussTwoPartDist head)
+    """Two HL-Gauss heads whose means add up to the value: the small head
+    learns the remainder of the target modulo 2, the large head the rest.
+    The tables (f32 arrays: an odd number >= 3 of centres, one more bound,
+    strictly increasing bounds) are module configuration, not trained and not
+    checkpointed.  kernel: HLGaussTwoPartDist's switch (None: its default)."""
+
+    def __init__(self, dtype, small_centers, small_bounds, large_centers, large_bounds,
+                 smoothness=0.75, weight_init=constant(0.0), kernel=None):
+        super().__init__()
+        self.dtype = canonical_dtype(dtype)
+        who = "HLGaussTwoPartCritic"
+        self.small_centers, self.small_bounds = _hlgauss_table(who, "small", small_centers,
+                                                               small_bounds)
+        self.large_centers, self.large_bounds = _hlgauss_table(who, "large", large_centers,
+                                                               large_bounds)
+        self.smoothness = float(smoothness)
+        self.weight_init = weight_init
+        self.kernel = kernel
+        self.num_small_bins = int(self.small_centers.size)
+        self.num_large_bins = int(self.large_centers.size)
+        self._tables = None
+        self.small_impl = _Dense(self.num_small_bins, True, self.dtype, weight_init)
+        self.large_impl = _Dense(self.num_large_bins, True, self.dtype, weight_init)
+
+    @staticmethod
+    def create(dtype, num_small_bins=127, num_large_bins=127, smoothness=0.75):
+        # 3 mantissa bits, 3 exponent bits, denormals; bias 7: centres up to
+        # 1.875, bias -3: centres 0, 2, ..., 14, 16, 18, ... up to 1920
+        small = _floating_point_bins(3, 3, 2 ** 3 - 1)
+        large = _floating_point_bins(3, 3, -3)
+        assert small[0].shape[0] == num_small_bins
+        assert large[0].shape[0] == num_large_bins
+        return HLGaussTwoPartCritic(dtype, *small, *large, smoothness=smoothness)
+
+    def forward(self, features, train=False):
+        from .dists import HLGaussDist, HLGaussTwoPartDist
+        # the tables on the features' device, copied once (no host copy inside
+        # a captured update)
+        if self._tables is None or self._tables[0].device != features.device:
+            self._tables = tuple(torch.from_numpy(a).to(features.device) for a in (
+                self.small_centers, self.small_bounds, self.large_centers, self.large_bounds))
+        t = self._tables
+        return HLGaussTwoPartDist(
+            HLGaussDist(self.small_impl(features), t[0], t[1], self.smoothness, kernel="torch"),
+            HLGaussDist(self.large_impl(features), t[2], t[3], self.smoothness, kernel="torch"),
+            kernel=self.kernel)

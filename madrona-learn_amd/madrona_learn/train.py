@@ -501,14 +501,14 @@ def _check_critic_flags(cfg, critic, form):
         from .models import DenseLayerCritic, DreamerV3Critic
         if not isinstance(critic, (DenseLayerCritic, DreamerV3Critic)):
             raise NotImplementedError(
-                f"hlgauss_critic=True with a {name} critic: HLGaussCritic (models.py:253-307) is "
-                "the HL-Gauss critic implemented here (HLGaussTwoPartCritic is not)")
+                f"hlgauss_critic=True with a {name} critic: HLGaussCritic (models.py:253-307) "
+                "and HLGaussTwoPartCritic (324-447) are the HL-Gauss critics implemented here")
     raise ValueError(
         f"TrainConfig.dreamer_v3_critic={dv3}, hlgauss_critic={hlg} but the policy's critic is "
         f"{name} ({form}): set dreamer_v3_critic={want[0]} and hlgauss_critic={want[1]} (an "
-        "HLGaussCritic needs dreamer_v3_critic=False: the reference tests dreamer_v3_critic, "
-        "True by default, first), or use DreamerV3Critic / DenseLayerCritic / HLGaussCritic to "
-        "match the flags")
+        "HLGaussCritic / HLGaussTwoPartCritic needs dreamer_v3_critic=False: the reference tests "
+        "dreamer_v3_critic, True by default, first), or use DreamerV3Critic / DenseLayerCritic / "
+        "HLGaussCritic / HLGaussTwoPartCritic to match the flags")
 
 
 def _fused_tree_problem(policy, rollout_state, sim_batch, cfg):
@@ -594,6 +594,11 @@ def _init_training_torch(device, cfg, policy, rollout_state, user_hooks, dp, ran
         ps = TorchPolicyState(ac, policy.obs_preprocess, device, obs_p, cfg.compute_dtype,
                               buckets, seed)
         _check_critic_flags(cfg, getattr(ac, "critic", None), ps.critic_form)
+        if cfg.normalize_values and ps.critic_bins > 1:
+            # (TorchPPO.prepare's refusal, before init_hyperparams' bare assert)
+            raise ValueError("normalize_values with a SymExpTwoHotDistribution / HLGaussDist / "
+                             "HLGaussTwoPartDist critic (the reference asserts against it, "
+                             "ppo.py:57)")
         dp.broadcast_(ps.params)
         algo = TorchPPO()
         ts = TorchTrainState(cfg, algo.init_hyperparams(cfg), ps,
