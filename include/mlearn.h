@@ -387,8 +387,16 @@ typedef struct mlearn_ppo_hparams {
                                               (2), 1 = register-staged (round 5: two
                                               chunks in flight through registers),
                                               2 = LDS-DMA pipeline (global_load_lds,
-                                              ML_WG_STAGES stages).  Same fragments in
-                                              the same order: bit-identical gradients */
+                                              ML_WG_STAGES stages), 4 = group-major: the
+                                              LDS-DMA pipeline with one workgroup per
+                                              (output tile, group of splits g, g + 16,
+                                              ...) for the MLP weights the plan gives
+                                              more than 16 splits, which leaves 16 f32
+                                              slabs per weight for the reduction; every
+                                              other weight as 2 (f32 policies: their one
+                                              form).  Same fragments and the same f32
+                                              additions in the same order: bit-identical
+                                              gradients.  3 is not a form (EINVAL) */
 } mlearn_ppo_hparams;
 
 /* Number of partials mlearn_ppo_hparams.grad_sumsq_out receives: one per 64
@@ -402,6 +410,16 @@ int64_t mlearn_ppo_workspace_bytes(const mlearn_mlp_policy* policy, int64_t rows
  * row count given mlearn_ppo_hparams.step_kernel = requested: 1 (feature-split)
  * or 2 (row-split); -1 for an invalid policy / request (host-only, no GPU). */
 int32_t mlearn_ppo_step_kernel(const mlearn_mlp_policy* policy, int64_t rows, int32_t requested);
+
+/* The weight-gradient form (1, 2 or 4) that MLP job `job` (0 .. num_layers - 1:
+ * the trunk weights, num_layers: the head) of a minibatch of `rows` rows runs
+ * in when mlearn_ppo_hparams.wgrad_form = requested, with its split-K plan:
+ * splits, rows per split, and the f32 slabs it leaves for the reduction (16
+ * in form 4, else splits; each out pointer may be NULL).  -1 for bad
+ * arguments. */
+int32_t mlearn_ppo_wgrad_plan(const mlearn_mlp_policy* policy, int64_t rows, int32_t requested,
+                              int32_t job, int32_t* splits, int64_t* rows_per_split,
+                              int32_t* slabs);
 
 /* One PPO minibatch step up to the flat gradient: forward (ActorCritic.update,
  * actor_critic.py:98-128), loss (ppo.py:129-262), backward (jax.value_and_grad,

@@ -52,7 +52,9 @@ int validate_lstm(const mlearn_mlp_policy* p, const mlearn_lstm* r) {
 
 // The kernels' view of the hyper-parameters for M rows per minibatch.
 static int make_hp(const mlearn_ppo_hparams& h, int64_t M, int num_groups, bool metrics, HpK* out) {
-    ML_REQUIRE(h.wgrad_form >= 0 && h.wgrad_form <= 2, "ppo: wgrad_form %d", h.wgrad_form);
+    // (3 is not a form: the group-major launch is 4)
+    ML_REQUIRE((h.wgrad_form >= 0 && h.wgrad_form <= 2) || h.wgrad_form == 4, "ppo: wgrad_form %d",
+               h.wgrad_form);
     HpK hp{};
     hp.clip = h.clip_coef;
     hp.vcoef = h.value_loss_coef;
@@ -66,7 +68,7 @@ static int make_hp(const mlearn_ppo_hparams& h, int64_t M, int num_groups, bool 
     hp.huber = h.huber_value_loss;
     hp.loss_scale = h.loss_scale;
     hp.metrics = metrics;
-    hp.wg_form = h.wgrad_form;
+    hp.wg_form = h.wgrad_form ? h.wgrad_form : ML_WG_FORM;  // 0: the library's choice
     hp.inv_s = (float)(1.0 / (double)M);
     hp.inv_sk = (float)(1.0 / ((double)M * num_groups));
     *out = hp;
@@ -129,7 +131,7 @@ static int launch_minibatch(const mlearn_mlp_policy& p, const mlearn_rollout_vie
     for (int l = 0; l < L; ++l)
         tab[l] = WgOperands{l == 0 ? p.obs_dim : H, H, l == 0 ? ws.x0 : ws.a[l - 1], ws.dz[l]};
     tab[L] = WgOperands{H, head_cols(p), ws.a[L - 1], ws.dhead};
-    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 1, ws), ws, hp, M, p.actions.num_groups,
+    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 1, ws, wg_groupable<T>(hp, L + 1)), ws, hp, M, p.actions.num_groups,
                                  loss_out, make_layout(p), grad, h.grad_sumsq_out, s))
         return rc;
     if (seq_weight && loss_out)  // 'Loss' from the weighted sums
@@ -186,7 +188,7 @@ static int launch_minibatch_lstm(const mlearn_mlp_policy& p, const mlearn_lstm& 
     tab[L] = WgOperands{H, head_cols(p), lw.hout, ws.dhead};
     tab[L + 1] = WgOperands{H, 4 * H, feat, lw.dg};
     tab[L + 2] = WgOperands{H, 4 * H, lw.hin, lw.dg};
-    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 3, ws), ws, hp, M, p.actions.num_groups,
+    if (int rc = launch_wgrad<T>(make_wg_jobs(tab, L + 3, ws, wg_groupable<T>(hp, L + 1)), ws, hp, M, p.actions.num_groups,
                                  loss_out, make_layout_lstm(p, lstm), grad, h.grad_sumsq_out, s))
         return rc;
     return check_launch("lstm_ppo_minibatch_grad");
@@ -225,6 +227,24 @@ int32_t mlearn_ppo_step_kernel(const mlearn_mlp_policy* policy, int64_t rows, in
                                         policy->hidden, policy->dtype == MLEARN_DTYPE_BF16);
     if (requested == 2 && !rows16) return -1;
     return rows16 && requested != 1 ? 2 : 1;
+}
+
+int32_t mlearn_ppo_wgrad_plan(const mlearn_mlp_policy* policy, int64_t rows, int32_t requested,
+                              int32_t job, int32_t* splits, int64_t* rows_per_split,
+                              int32_t* slabs) {
+    if (validate_policy(policy) || rows < 1 || requested < 0 || requested == 3 || requested > 4 ||
+        job < 0 ||
+        job > policy->num_layers)
+        return -1;
+    WsK ws;
+    carve(*policy, rows, nullptr, &ws);
+    const bool bf = policy->dtype == MLEARN_DTYPE_BF16;
+    const int form = bf ? (requested ? requested : ML_WG_FORM) : 1;
+    const bool grouped = form == 4 && ws.splits[job] > kRgGroups;
+    if (splits) *splits = ws.splits[job];
+    if (rows_per_split) *rows_per_split = ws.rps[job];
+    if (slabs) *slabs = grouped ? kRgGroups : ws.splits[job];
+    return form == 4 && !grouped ? 2 : form;
 }
 
 // The argument checks the feed-forward and the recurrent update share; who

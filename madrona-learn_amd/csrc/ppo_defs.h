@@ -57,6 +57,9 @@ constexpr int kRowAlign = 64;  // Mp granularity of the update (an even number o
 #ifndef ML_WG_WAVES
 #define ML_WG_WAVES 3  // waves per SIMD the weight-gradient kernel is register-budgeted for
 #endif
+#ifndef ML_WG_FORM
+#define ML_WG_FORM 2  // what mlearn_ppo_hparams.wgrad_form 0 selects (f32 runs its one form)
+#endif
 constexpr int kMaxJobs = MLEARN_MAX_LAYERS + 3;  // weight-gradient jobs
 
 // LSTM scan buffers of the recurrent update (rows f = t * mb + m, compute

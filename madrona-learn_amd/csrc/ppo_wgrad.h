@@ -27,6 +27,7 @@ struct WgJob {
     float* out;
     int64_t rps;
     int I, J, ti, tj, splits, wg0;
+    int grouped;  // wgrad_form 4: one workgroup per (tile, split group), kRgGroups slabs
 };
 struct WgJobs {
     WgJob job[kMaxJobs];
@@ -371,6 +372,233 @@ __device__ inline void wgrad_tile_glds(const WgJobs& jobs, const WgJob& J, int l
             }
 }
 
+// ---------------------------------------------------------------------------
+// The group-major bf16 weight-gradient tile (mlearn_ppo_hparams.wgrad_form 4).
+// reduce_grads' split group g sums the slabs of splits g, g + 16, g + 32, ...
+// in that order, starting from 0.f, before the 16 group values meet.  Here
+// one workgroup owns (output tile, group g) and forms that group value
+// itself: it walks the group's splits in order, each split from zeroed MFMA
+// accumulators over the split's own rows (the plan's rps, 32-row chunks, the
+// k-steps of wgrad_tile_glds), and after each split adds the accumulators to
+// a running f32 sum that starts at 0.f.  It stores one slab per group, so
+// reduce_grads finds kRgGroups slabs instead of `splits` and adds them in the
+// order it always did: the flat gradient keeps its bits while the slab
+// traffic of both launches falls by splits / 16.
+//
+// Output tile TI x TJ per workgroup (four waves in 2 x 2, each TI/2 x TJ/2),
+// smaller than the per-split form's 128 x 128 because a workgroup now has
+// splits / 16 times the rows.  The chunks of all the group's splits form one
+// LDS-DMA stream, S stages of R chunks deep (one barrier per stage: with one
+// MFMA block per wave a 32-row stage is all barrier and LDS latency), so the
+// pipeline does not drain at a split boundary.  Operand images, swizzle and fragment reads as wgrad_tile_glds.
+// ---------------------------------------------------------------------------
+#ifndef ML_WGG_TI
+#define ML_WGG_TI 128  // group-major output tile rows
+#endif
+#ifndef ML_WGG_TJ
+#define ML_WGG_TJ 64  // group-major output tile columns
+#endif
+#ifndef ML_WGG_STAGES
+#define ML_WGG_STAGES 2  // group-major LDS stages (S - 1 in flight)
+#endif
+#ifndef ML_WGG_R
+#define ML_WGG_R 4  // group-major: 32-row chunks per LDS stage (one barrier per stage)
+#endif
+struct WgGroupsCfg {
+    static constexpr int TI = ML_WGG_TI, TJ = ML_WGG_TJ, S = ML_WGG_STAGES, R = ML_WGG_R;
+    static_assert((TI == 64 || TI == 128) && (TJ == 64 || TJ == 128), "operand image rows of 128 / 256 B");
+    static constexpr size_t tile_lds = (size_t)S * R * 32 * 2 * (TI + TJ);
+    // the launch also runs the per-split LDS-DMA tile for the jobs that are not grouped
+    static constexpr size_t lds = tile_lds > WgCfg<bf16>::glds ? tile_lds : WgCfg<bf16>::glds;
+};
+
+template <int TI, int TJ, int S, int R>
+__device__ inline void wgrad_tile_groups(const WgJobs& jobs, const WgJob& J, int local, char* smem) {
+    static_assert(S >= 2, "at least two stages");
+    constexpr int CH = 32, PX = 2 * TI, PY = 2 * TJ;
+    constexpr int XB = CH * PX, YB = CH * PY, SB = XB + YB;
+    constexpr int NXW = XB / 1024 / 4, NYW = YB / 1024 / 4;
+    constexpr int G = NXW + NYW;
+    constexpr int AI = TI / 64, BJ = TJ / 64;  // MFMA blocks per wave
+    static_assert(G * R * (S - 2) < 64, "vmcnt range");
+    const int nt = J.ti * J.tj;
+    int g, t;
+    if ((J.wg0 & 7) == 0) {
+        // XCD-aware, as wgrad_tile: the nt tiles of one group walk the same
+        // rows at the same time and get block ids 8 apart (speed only)
+        const int x = local & 7, q = local >> 3;
+        t = q % nt;
+        g = (q / nt) * 8 + x;
+    } else {
+        g = local / nt;
+        t = local - g * nt;
+    }
+    const int i0 = (t % J.ti) * TI, j0 = (t / J.ti) * TJ;
+    // the group's chunk stream: splits g, g + 16, ... of `per` chunks each;
+    // only the plan's last split can be shorter, and it ends its group's stream
+    const int per = (int)(J.rps / CH);
+    const int nsp = (J.splits - g + kRgGroups - 1) / kRgGroups;
+    const int64_t lm0 = (int64_t)(g + kRgGroups * (nsp - 1)) * J.rps;
+    const int64_t lm1 = lm0 + J.rps < jobs.Mp ? lm0 + J.rps : jobs.Mp;
+    const int total = (nsp - 1) * per + (int)((lm1 - lm0) / CH);
+    const bf16* X = (const bf16*)J.X;
+    const bf16* Y = (const bf16*)J.Y;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int iw = (w & 1) * (TI / 2), jw = (w >> 1) * (TJ / 2);
+    const bool on = i0 + iw < J.I && j0 + jw < J.J;
+
+    int ox[NXW], oy[NYW];
+#pragma unroll
+    for (int k = 0; k < NXW; ++k) {
+        const int b = (w * NXW + k) * 1024 + lane * 16, r = b / PX;
+        const int u = ((b % PX) >> 4) ^ wg_swz<PX>(r);
+        const int col = i0 + 8 * u < J.I ? i0 + 8 * u : i0;
+        ox[k] = r * J.I + col;
+    }
+#pragma unroll
+    for (int k = 0; k < NYW; ++k) {
+        const int b = (w * NYW + k) * 1024 + lane * 16, r = b / PY;
+        const int u = ((b % PY) >> 4) ^ wg_swz<PY>(r);
+        const int col = j0 + 8 * u < J.J ? j0 + 8 * u : j0;
+        oy[k] = r * J.J + col;
+    }
+    const uint32_t lbase =
+        (uint32_t)(size_t)(const __attribute__((address_space(3))) char*)smem;
+    // next chunk of the stream: its first row, its index within its split, its stage
+    int64_t irow = (int64_t)g * J.rps;
+    int ic = 0, islot = 0, issued = 0;
+    auto issue_chunk = [&]() {
+        const bf16* xb = X + irow * J.I;
+        const bf16* yb = Y + irow * J.J;
+        const uint32_t sb = lbase + (uint32_t)(islot * SB);
+#pragma unroll
+        for (int k = 0; k < NXW; ++k)
+            wg_glds16(xb + ox[k], __builtin_amdgcn_readfirstlane(sb + (uint32_t)((w * NXW + k) * 1024)));
+#pragma unroll
+        for (int k = 0; k < NYW; ++k)
+            wg_glds16(yb + oy[k],
+                      __builtin_amdgcn_readfirstlane(sb + (uint32_t)(XB + (w * NYW + k) * 1024)));
+        irow += CH;
+        if (++ic == per) {  // on to split + 16
+            ic = 0;
+            irow += (int64_t)(kRgGroups - 1) * J.rps;
+        }
+        islot = islot + 1 == S * R ? 0 : islot + 1;
+        ++issued;
+    };
+    // one stage: the stream's next R chunks (fewer at its end; the slots stay R apart)
+    auto issue = [&]() {
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (issued < total) issue_chunk();
+            else islot = islot + 1 == S * R ? 0 : islot + 1;
+        }
+    };
+
+    const int lg = lane >> 4, hh = lg >> 1, cc = lg & 1, q = (lane >> 2) & 3, p = lane & 3;
+    auto fofs = [&](int c0, int P, int swz) {
+        const int u = (c0 >> 3) + 2 * cc + (p >> 1);
+        return (8 * hh + q) * P + ((u ^ swz) << 4) + (p & 1) * 8;
+    };
+    int fx[AI], fy[BJ];
+#pragma unroll
+    for (int a = 0; a < AI; ++a) fx[a] = fofs(iw + 32 * a, PX, wg_swz<PX>(q));
+#pragma unroll
+    for (int b = 0; b < BJ; ++b) fy[b] = fofs(jw + 32 * b, PY, wg_swz<PY>(q));
+    typedef __attribute__((address_space(3))) short4v* lp;
+    typedef short short8v __attribute__((ext_vector_type(8)));
+    auto frag = [&](const char* base, int ofs, int ks, int P) {
+        const char* a = base + ks * 16 * P + ofs;
+        short4v lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(a));
+        short4v hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lp)(a + 4 * P));
+        short8v v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+        return __builtin_bit_cast(bf16x8, v);
+    };
+    f32x16 acc[AI][BJ], sum[AI][BJ];
+#pragma unroll
+    for (int a = 0; a < AI; ++a) {
+        zero_acc<BJ>(acc[a]);
+        zero_acc<BJ>(sum[a]);
+    }
+
+    const int nst = (total + R - 1) / R;  // stages of the stream
+#pragma unroll
+    for (int k = 0; k < S - 1; ++k)
+        if (k < nst) issue();
+    int st = 0, cs = 0;  // stage of iteration it, the next chunk's index within its split
+    for (int it = 0; it < nst; ++it) {
+        // stage it has landed (this wave's pieces): the S - 2 younger stages
+        // may stay in flight where all of them are whole
+        if ((it + S - 1) * R <= total) wg_vmcnt<G * R * (S - 2)>();
+        else wg_vmcnt<0>();
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();  // every wave's pieces in; stage (it - 1) % S read out
+        __builtin_amdgcn_sched_barrier(0);
+        if (it + S - 1 < nst) issue();
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            if (it * R + r >= total) break;
+            if (on) {
+                const char* xs = smem + (st * R + r) * SB;
+                const char* ys = xs + XB;
+#pragma unroll
+                for (int ks = 0; ks < CH / 16; ++ks) {
+                    bf16x8 fa[AI], fb[BJ];
+#pragma unroll
+                    for (int a = 0; a < AI; ++a) fa[a] = frag(xs, fx[a], ks, PX);
+#pragma unroll
+                    for (int b = 0; b < BJ; ++b) fb[b] = frag(ys, fy[b], ks, PY);
+#pragma unroll
+                    for (int a = 0; a < AI; ++a)
+#pragma unroll
+                        for (int b = 0; b < BJ; ++b)
+                            acc[a][b] = MT<bf16>::mma(fa[a], fb[b], acc[a][b]);
+                }
+            }
+            if (++cs == per || it * R + r + 1 == total) {
+                // end of a split: reduce_grads' v += slab[split] (the first one onto 0.f)
+                cs = 0;
+#pragma unroll
+                for (int a = 0; a < AI; ++a)
+#pragma unroll
+                    for (int b = 0; b < BJ; ++b) {
+                        sum[a][b] = sum[a][b] + acc[a][b];
+#pragma unroll
+                        for (int e = 0; e < 16; ++e) acc[a][b][e] = 0.f;
+                    }
+            }
+        }
+        st = st + 1 == S ? 0 : st + 1;
+    }
+    if (!on) return;
+    float* out = J.out + (int64_t)g * J.I * J.J;
+#pragma unroll
+    for (int a = 0; a < AI; ++a)
+#pragma unroll
+        for (int b = 0; b < BJ; ++b)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int i = i0 + iw + 32 * a + acc_row(e, lane);
+                const int j = j0 + jw + 32 * b + (lane & 31);
+                if (i < J.I && j < J.J)
+                    __builtin_nontemporal_store(sum[a][b][e], out + (int64_t)i * J.J + j);
+            }
+}
+
+// The per-split LDS-DMA tile of one job: operand image rows of 128 B (<= 64
+// columns) or 256 B.
+__device__ inline void wgrad_job_glds(const WgJobs& jobs, const WgJob& J, int local, char* smem) {
+    static_assert(kWgTile == 128, "LDS-DMA tile shape");
+    if (J.I <= 64) {
+        if (J.J <= 64) wgrad_tile_glds<128, 128, 32>(jobs, J, local, smem);
+        else wgrad_tile_glds<128, 256, 32>(jobs, J, local, smem);
+    } else {
+        if (J.J <= 64) wgrad_tile_glds<256, 128, 32>(jobs, J, local, smem);
+        else wgrad_tile_glds<256, 256, 32>(jobs, J, local, smem);
+    }
+}
+
 // Blocks [0, nwg) compute weight gradients; the next ncol blocks the first
 // level of the column partials; one more (if loss_out) the loss metrics.
 // (The fixed-order reduction into the flat gradient is the next launch,
@@ -390,21 +618,32 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ML_WG_WAVES
     while (jb + 1 < jobs.n && (int)blockIdx.x >= jobs.job[jb + 1].wg0) ++jb;
     const WgJob& J = jobs.job[jb];
     if constexpr (sizeof(T) == 2) {
-        static_assert(kWgTile == 128, "LDS-DMA tile shape");
-        if (hp.wg_form != 1) {  // mlearn_ppo_hparams.wgrad_form: 0 / 2 = LDS-DMA
-            // operand image rows of 128 B (<= 64 columns) or 256 B
-            const int local = blockIdx.x - J.wg0;
-            if (J.I <= 64) {
-                if (J.J <= 64) wgrad_tile_glds<128, 128, 32>(jobs, J, local, smem);
-                else wgrad_tile_glds<128, 256, 32>(jobs, J, local, smem);
-            } else {
-                if (J.J <= 64) wgrad_tile_glds<256, 128, 32>(jobs, J, local, smem);
-                else wgrad_tile_glds<256, 256, 32>(jobs, J, local, smem);
-            }
+        if (hp.wg_form != 1) {  // mlearn_ppo_hparams.wgrad_form: 2 = LDS-DMA
+            wgrad_job_glds(jobs, J, blockIdx.x - J.wg0, smem);
             return;
         }
     }
     wgrad_tile<T>(jobs, J, blockIdx.x - J.wg0, smem);
+}
+
+// The launch of wgrad_form 4 (bf16): the grouped jobs' workgroups run the
+// group-major tile, every other job's the per-split LDS-DMA tile of form 2;
+// column-partial and loss blocks as wgrad_kernel.
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ML_WG_WAVES, 8))) void
+wgrad_groups_kernel(WgJobs jobs, WsK ws, HpK hp, int64_t M, int K, float* loss_out) {
+    if ((int)blockIdx.x >= jobs.nwg) {
+        const int b = blockIdx.x - jobs.nwg;
+        if (b < jobs.ncol) colsum_block(ws, b % jobs.ncolx, b / jobs.ncolx);
+        else loss_block(ws, hp, M, K, loss_out);
+        return;
+    }
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    int jb = 0;
+    while (jb + 1 < jobs.n && (int)blockIdx.x >= jobs.job[jb + 1].wg0) ++jb;
+    const WgJob& J = jobs.job[jb];
+    const int local = blockIdx.x - J.wg0;
+    if (J.grouped) wgrad_tile_groups<WgGroupsCfg::TI, WgGroupsCfg::TJ, WgGroupsCfg::S, WgGroupsCfg::R>(jobs, J, local, smem);
+    else wgrad_job_glds(jobs, J, local, smem);
 }
 
 // First level of the per-tile column partials (LayerNorm scale/bias grads,
@@ -508,15 +747,38 @@ template <typename T>
 static int launch_wgrad(const WgJobs& jobs, const WsK& ws, const HpK& hp, int64_t M, int K,
                         float* loss_out, const LayoutK& Lk, float* grad, double* sumsq,
                         hipStream_t s) {
-    // (once per instantiation and device, kept out of graph capture)
-    if (int rc = set_lds_attr((const void*)wgrad_kernel<T>, (int)WgCfg<T>::lds, "ppo_wgrad"))
-        return rc;
     const int blocks = jobs.nwg + jobs.ncol + (loss_out ? 1 : 0);
-    hipLaunchKernelGGL((wgrad_kernel<T>), dim3(blocks), dim3(256), WgCfg<T>::lds, s, jobs, ws, hp, M,
-                       K, loss_out);
+    // reduce_grads' view of the slabs: a grouped job left kRgGroups of them,
+    // and every job's slabs start where make_wg_jobs put them
+    WsK rws = ws;
+    bool grouped = false;
+    for (int l = 0; l < jobs.n; ++l) {
+        const WgJob& J = jobs.job[l];
+        grouped |= J.grouped != 0;
+        rws.splits[l] = J.grouped ? kRgGroups : J.splits;
+        rws.slab_off[l] = J.out - ws.slab;
+    }
+    // (the LDS attribute: once per kernel and device, kept out of graph capture)
+    if (grouped) {
+        if (int rc = set_lds_attr((const void*)wgrad_groups_kernel, (int)WgGroupsCfg::lds, "ppo_wgrad_groups"))
+            return rc;
+        hipLaunchKernelGGL(wgrad_groups_kernel, dim3(blocks), dim3(256), WgGroupsCfg::lds, s, jobs, ws, hp,
+                           M, K, loss_out);
+    } else {
+        if (int rc = set_lds_attr((const void*)wgrad_kernel<T>, (int)WgCfg<T>::lds, "ppo_wgrad"))
+            return rc;
+        hipLaunchKernelGGL((wgrad_kernel<T>), dim3(blocks), dim3(256), WgCfg<T>::lds, s, jobs, ws, hp,
+                           M, K, loss_out);
+    }
     hipLaunchKernelGGL(reduce_grads_kernel, dim3((unsigned)((Lk.total + 63) / 64)), dim3(256), 0, s,
-                       Lk, ws, grad, sumsq);
+                       Lk, rws, grad, sumsq);
     return MLEARN_OK;
+}
+
+// Leading jobs of a table that wgrad_form 4 may group (the MLP trunk and head
+// weights; the LSTM gate weights keep the per-split tile): bf16 only.
+template <typename T> static int wg_groupable(const HpK& hp, int n) {
+    return sizeof(T) == 2 && hp.wg_form == 4 ? n : 0;
 }
 
 // One weight-gradient job per table row (dW = X^T Y, I x J), in slab order:
@@ -525,24 +787,33 @@ struct WgOperands {
     int I, J;
     const void *X, *Y;
 };
-static WgJobs make_wg_jobs(const WgOperands* tab, int n, const WsK& ws) {
+// groupable: the first `groupable` jobs take the group-major form (wgrad_form
+// 4) when the plan gives them more than kRgGroups splits; their slabs shrink
+// to kRgGroups, and the later jobs' slabs follow (the area carved for the
+// plan's splits is never exceeded).
+static WgJobs make_wg_jobs(const WgOperands* tab, int n, const WsK& ws, int groupable = 0) {
     WgJobs jobs{};
     jobs.n = n;
     jobs.Mp = ws.Mp;
     int wg = 0;
+    int64_t so = 0;
     for (int l = 0; l < n; ++l) {
         WgJob& J = jobs.job[l];
         J.I = tab[l].I;
         J.J = tab[l].J;
         J.X = tab[l].X;
         J.Y = tab[l].Y;
-        J.out = ws.slab + ws.slab_off[l];
         J.rps = ws.rps[l];
-        J.ti = (J.I + kWgTile - 1) / kWgTile;
-        J.tj = (J.J + kWgTile - 1) / kWgTile;
         J.splits = ws.splits[l];
+        J.grouped = l < groupable && J.splits > kRgGroups;
+        const int ti = J.grouped ? WgGroupsCfg::TI : kWgTile, tj = J.grouped ? WgGroupsCfg::TJ : kWgTile;
+        const int slabs = J.grouped ? kRgGroups : J.splits;
+        J.out = ws.slab + so;
+        so += (int64_t)slabs * J.I * J.J;
+        J.ti = (J.I + ti - 1) / ti;
+        J.tj = (J.J + tj - 1) / tj;
         J.wg0 = wg;
-        wg += J.ti * J.tj * J.splits;
+        wg += J.ti * J.tj * slabs;
     }
     jobs.nwg = wg;
     jobs.ncolx = (ws.CP + 255) / 256;

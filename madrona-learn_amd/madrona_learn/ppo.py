@@ -66,8 +66,9 @@ class PPO(AlgoBase):  # ppo.py:49-106
     # choice (mlearn_ppo_step_kernel), 1 the feature split, 2 the row split
     # (A/B runs; 2 raises where the row split does not apply)
     step_kernel = 0
-    # mlearn_ppo_hparams.wgrad_form (ABI 22): 0 the library's choice (the
-    # LDS-DMA pipeline), 1 register-staged, 2 LDS-DMA; bit-identical (A/B runs)
+    # mlearn_ppo_hparams.wgrad_form (ABI 22): 0 the library's choice, 1
+    # register-staged, 2 LDS-DMA, 4 LDS-DMA with one workgroup per group of
+    # splits (16 slabs per weight); bit-identical (A/B runs)
     wgrad_form = 0
 
     def init_hyperparams(self, cfg):
