@@ -856,6 +856,54 @@ int mlearn_hlgauss_loss_bwd(const mlearn_hlgauss_tables* tables, const void* log
                             mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* LayerNorm + activation (models.py:46-56 LayerNorm and the ReLU / leaky  */
+/* ReLU that follows it in MLP and the entity encoder); the torch path's   */
+/* trunk normalisation (additive exports)                                  */
+/* ---------------------------------------------------------------------- */
+/* Per row of x [rows][features], statistics in f32 (flax's fast variance):
+ *   mean = sum(x) / F, rstd = 1 / sqrt(max(sum(x^2) / F - mean^2, 0) + eps),
+ *   z = (x - mean) (rstd scale) + bias, rounded to `dtype`,
+ *   y = act(z), rounded to `dtype`;
+ * act 0: none, 1: ReLU, 2: leaky ReLU of slope 0.01.  x, y, dy, dx:
+ * [rows][features] in `dtype` (MLEARN_DTYPE_F32 / MLEARN_DTYPE_BF16) with unit
+ * column stride and row strides ldx, ldy, lddy, lddx >= features in elements
+ * (a column range of a wider tensor passes without a copy), any base
+ * alignment: where every base pointer is 16-byte aligned and features and
+ * the row strides are multiples of 16 bytes of elements the rows move as
+ * 16-byte accesses, elsewhere element by element, with the same bits;
+ * columns from `features` on are neither read nor written.  scale, bias,
+ * dscale, dbias: contiguous f32 [features]; mean, rstd: contiguous f32 [rows].
+ * features 1..1024 and rows >= 1; anything else (a null pointer, a row stride
+ * below features, another dtype or act, eps that is not positive and finite)
+ * is MLEARN_EINVAL before the device is touched.  Nothing is allocated, no host
+ * synchronisation, no atomics. */
+int mlearn_layernorm_fwd(const void* x, int64_t ldx, int32_t dtype, const float* scale,
+                         const float* bias, int64_t rows, int32_t features, float eps,
+                         int32_t act, void* y, int64_t ldy, float* mean, float* rstd,
+                         mlearn_stream_t stream);
+/* Bytes of the backward's workspace (pure host, an upper bound for every
+ * device): a multiple of 2 * features * 4, at most 2048 partial rows;
+ * negative where the kernels do not apply (features outside 1..1024,
+ * rows < 1). */
+int64_t mlearn_layernorm_workspace_bytes(int64_t rows, int32_t features);
+/* The gradient, x_hat = (x - mean) rstd and the activation's mask (the sign of
+ * the rounded z) recomputed from x, mean, rstd, scale and bias:
+ *   g = dy act'(z), w = g scale,
+ *   dx = rstd (w - mean_F(w) - x_hat mean_F(w x_hat)), rounded once,
+ *   dbias = sum_rows g, dscale = sum_rows g x_hat
+ * (at the variance clamp the fast variance's own gradient is multiplied by
+ * x - mean = 0, so this is the module's gradient).  Each workgroup sums a
+ * fixed, contiguous share of the rows into one [2][features] row of
+ * `workspace` (mlearn_layernorm_workspace_bytes, 4-byte aligned) and a second
+ * launch adds those rows in a fixed order: dscale and dbias depend on (rows,
+ * features, the device's CU count) only, the same bits on every call. */
+int mlearn_layernorm_bwd(const void* x, int64_t ldx, int32_t dtype, const float* scale,
+                         const float* bias, const float* mean, const float* rstd, const void* dy,
+                         int64_t lddy, int64_t rows, int32_t features, int32_t act, void* dx,
+                         int64_t lddx, float* dscale, float* dbias, void* workspace,
+                         mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Synthetic dummy vec-env (test/bench sim plugin, not part of the         */
 /* reference: stands in for the Madrona sim_fns['step'] custom call,       */
 /* rollouts.py:905-936).                                                   */

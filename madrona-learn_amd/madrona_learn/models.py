@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import attention as _attention
+from . import layernorm as _layernorm
 from .cfg import ContinuousActionsConfig, DiscreteActionsConfig, canonical_dtype
 
 def orthogonal(scale=1.0):
@@ -95,22 +96,32 @@ class _Dense(nn.Module):
 
 
 class LayerNorm(nn.Module):  # models.py:46-56 (flax nn.LayerNorm: eps 1e-6, f32 statistics)
-    def __init__(self, dtype):
+    """forward(x, act): the normalisation and, fused behind it, the caller's
+    activation (None, "relu" or "leaky_relu" of slope 0.01) on the cast result.
+
+    layer_norm_kernel (class attribute, as SelfAttention.attention_kernel; the
+    constructor's kernel overrides it for one module): 0 = the library's
+    choice, 1 = the torch composition, 2 = the HIP kernel
+    (NotImplementedError where it does not apply: CPU tensors, fp16, inputs of
+    another dtype than the module's, more than 1024 features, an empty
+    tensor)."""
+
+    layer_norm_kernel = 0
+
+    def __init__(self, dtype, kernel=None):
         super().__init__()
         self.dtype = canonical_dtype(dtype)
+        self.kernel = kernel
         self.scale = None
         self.bias = None
 
-    def forward(self, x):
+    def forward(self, x, act=None):
         F = x.shape[-1]
         if self.scale is None:
             self.scale = nn.Parameter(torch.ones(F, device=x.device))
             self.bias = nn.Parameter(torch.zeros(F, device=x.device))
-        xf = x.float()
-        mean = xf.mean(-1, keepdim=True)
-        var = torch.clamp((xf * xf).mean(-1, keepdim=True) - mean * mean, min=0.0)  # fast variance
-        y = (xf - mean) * (torch.rsqrt(var + 1e-6) * self.scale) + self.bias
-        return y.to(self.dtype)
+        kernel = type(self).layer_norm_kernel if self.kernel is None else self.kernel
+        return _layernorm.layer_norm(x, self.scale, self.bias, self.dtype, act, kernel)
 
 
 class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU per layer
@@ -127,7 +138,7 @@ class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU p
     def forward(self, inputs, train=False):
         x = inputs
         for d, n in zip(self.dense, self.norms):
-            x = torch.relu(n(d(x)))
+            x = n(d(x), act="relu")
         return x
 
 
@@ -191,7 +202,7 @@ class _EntityEmbed(nn.Module):  # models.py:463-478: Dense (no bias) -> LayerNor
         self.norm = LayerNorm(dtype)
 
     def forward(self, x):
-        return nn.functional.leaky_relu(self.norm(self.dense(x)))
+        return self.norm(self.dense(x), act="leaky_relu")
 
 
 class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use entity encoder)
@@ -248,7 +259,7 @@ class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use
             attended = attended + embedded
         attended = self.attended_norm(attended.mean(dim=-2))
 
-        ff = nn.functional.leaky_relu(self.ff_norm(self.ff_0(attended)))
+        ff = self.ff_norm(self.ff_0(attended), act="leaky_relu")
         ff = nn.functional.leaky_relu(self.ff_1(ff))  # (a transformer block has no activation here)
         return self.out_norm(attended + ff)
 
