@@ -904,6 +904,47 @@ int mlearn_layernorm_bwd(const void* x, int64_t ldx, int32_t dtype, const float*
                          mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* LSTM sequence (rnn.py MultiLayerLSTMCell / LSTM.sequence): the          */
+/* recurrent part of one layer over a BPTT chunk on the torch path         */
+/* (additive exports)                                                      */
+/* ---------------------------------------------------------------------- */
+/* For t = 0 .. T-1, per row n and unit u (gates i, f, g, o in column blocks
+ * of `hidden` = R):
+ *   z_t = zx_t + (hin_t . wh + b)            (f32, MFMA product)
+ *   i, f, o = sigmoid(z), g = tanh(z)        each rounded to `dtype`
+ *   c_t = f cin_t + i g, h_t = o tanh(c_t)   each rounded to `dtype`
+ * where (hin_0, cin_0) = (h0, c0) and (hin_{t+1}, cin_{t+1}) = (h_t, c_t),
+ * zero in the rows where seq_ends[t][n] != 0; hs holds h_t before clearing.
+ * zx, gates: [T][N][4R]; hs, cs, hprev: [T][N][R]; h0, c0: [N][R]; wh: [R][4R];
+ * b: [4R]; all contiguous in `dtype` (MLEARN_DTYPE_F32 / MLEARN_DTYPE_BF16) and
+ * 16-byte aligned; seq_ends: [T][N] bytes or null (no clears).  gates receives
+ * the four activations, hprev the rows hin_t (the weight gradient's operand,
+ * dwh = hprev^T dG).  hidden: a multiple of 32 in 32..512; N >= 1 (rows from N
+ * on in the last tile of 32 are neither read nor written); T >= 1; anything
+ * else is MLEARN_EINVAL before the device is touched.  One small launch re-lays
+ * wh into `workspace` (mlearn_lstm_seq_workspace_bytes, 16-byte aligned), then
+ * one launch per step; nothing is allocated, no host synchronisation, no
+ * atomics: the same inputs give the same bits. */
+int mlearn_lstm_seq_fwd(const void* zx, const void* wh, const void* b, const void* h0,
+                        const void* c0, const uint8_t* seq_ends, int32_t T, int64_t N,
+                        int32_t hidden, int32_t dtype, void* hs, void* cs, void* gates,
+                        void* hprev, void* workspace, mlearn_stream_t stream);
+/* Bytes of the workspace of either call (pure host): the weight image and one
+ * f32 [N][hidden] carry; negative where the kernels do not apply. */
+int64_t mlearn_lstm_seq_workspace_bytes(int64_t N, int32_t hidden, int32_t dtype);
+/* The reverse scan from dhs [T][N][R] (the cotangent of hs) and the forward's
+ * cs and gates: dg [T][N][4R] = the gradient with respect to z_t (= dzx, and
+ * the operand of dwh = hprev^T dg, db = sum_rows dg, dwi = x^T dg), dh0 and
+ * dc0 [N][R], all in `dtype`, dg and dh0 rounded once.  The carry cotangents
+ * from step t+1 (dh = dg_{t+1} wh^T and the f32 dc) enter step t only in the
+ * rows where seq_ends[t][n] == 0.  The four K quarters of the product are
+ * added in a fixed order: the same bits on every call. */
+int mlearn_lstm_seq_bwd(const void* dhs, const void* wh, const void* c0, const uint8_t* seq_ends,
+                        const void* cs, const void* gates, int32_t T, int64_t N, int32_t hidden,
+                        int32_t dtype, void* dg, void* dh0, void* dc0, void* workspace,
+                        mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Synthetic dummy vec-env (test/bench sim plugin, not part of the         */
 /* reference: stands in for the Madrona sim_fns['step'] custom call,       */
 /* rollouts.py:905-936).                                                   */

@@ -284,6 +284,11 @@ _SIGNATURES = {
                                        c_int32, _P, c_int64, _P, _P, _S]),
     "mlearn_layernorm_bwd": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, c_int64, c_int64,
                                        c_int32, c_int32, _P, c_int64, _P, _P, _P, _S]),
+    "mlearn_lstm_seq_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
+    "mlearn_lstm_seq_fwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
+                                      _P, _P, _P, _P, _P, _S]),
+    "mlearn_lstm_seq_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
+                                      _P, _P, _P, _P, _S]),
     "mlearn_dummy_env_step": (c_int32, [_P, _P, c_int32, c_int64, c_int32, c_uint32, c_uint32,
                                         c_uint32, _P, _P, _P, _S]),
     "mlearn_dummy_env_reset": (c_int32, [_P, c_int64, c_int32, c_uint32, c_uint32, c_uint32, _P,

@@ -18,6 +18,7 @@ import numpy as np
 import torch
 from torch import nn
 
+from . import lstm_seq as _lstm_seq
 from .cfg import canonical_dtype
 from .models import _init_rng, orthogonal
 
@@ -69,18 +70,57 @@ class MultiLayerLSTMCell(nn.Module):  # rnn.py:10-45
 
 
 class LSTM(nn.Module):  # rnn.py:47-111
-    def __init__(self, num_hidden_channels, num_layers, dtype):
+    """lstm_kernel (class attribute, as LayerNorm.layer_norm_kernel; the
+    constructor's kernel overrides it for one module): 0 = the library's
+    choice, 1 = the torch composition, 2 = the HIP kernels of lstm_seq.py
+    (NotImplementedError where they do not apply: CPU tensors, fp16, inputs of
+    another dtype than the module's, a width that is no multiple of 32 in
+    32..512, an empty tensor).  With the HIP kernels ``sequence`` runs layer by
+    layer (layer l over all steps, then layer l + 1 on its outputs: the stacked
+    cell feeds h_t of layer l into layer l + 1 at the same t only) and
+    ``forward`` is one step of the forward kernel where gradients are disabled
+    (the composition where they are enabled)."""
+
+    lstm_kernel = 0
+
+    def __init__(self, num_hidden_channels, num_layers, dtype, kernel=None):
         super().__init__()
         self.num_hidden_channels = int(num_hidden_channels)
         self.num_layers = int(num_layers)
         self.dtype = canonical_dtype(dtype)
+        self.kernel = kernel
         self.cell = MultiLayerLSTMCell(num_hidden_channels, num_layers, dtype)
 
+    def _use_hip(self, hiddens, x):
+        kernel = type(self).lstm_kernel if self.kernel is None else self.kernel
+        return _lstm_seq.use_hip(kernel, x, hiddens[1][0], hiddens[0][0], self.dtype,
+                                 self.num_hidden_channels)
+
+    def _layers_hip(self, hiddens, seq_ends, seq_x):
+        """Every layer over seq_x [T, N, F] by the HIP kernels: per layer (hs, cs)."""
+        cell = self.cell
+        if len(cell.wi) == 0:
+            cell._init(seq_x.shape[-1], seq_x.device)
+        in_c, in_h = hiddens
+        x, out = seq_x, []
+        for l in range(self.num_layers):
+            hs, cs = _lstm_seq.lstm_layer_hip(x, cell.wi[l], cell.wh[l], cell.b[l], in_h[l],
+                                              in_c[l], seq_ends, self.dtype)
+            out.append((hs, cs))
+            x = hs
+        return out
+
     def forward(self, cur_hiddens, in_features, train=False):  # rnn.py:77-79
+        if self._use_hip(cur_hiddens, in_features) and not torch.is_grad_enabled():
+            out = self._layers_hip(cur_hiddens, None, in_features.unsqueeze(0))
+            return (torch.cat([hs[0] for hs, _ in out], -1),
+                    ([cs[0] for _, cs in out], [hs[0] for hs, _ in out]))
         new_hiddens, out = self.cell(cur_hiddens, in_features)
         return out, new_hiddens
 
     def sequence(self, start_hiddens, seq_ends, seq_x, train=False):  # rnn.py:81-111
+        if self._use_hip(start_hiddens, seq_x):
+            return torch.cat([hs for hs, _ in self._layers_hip(start_hiddens, seq_ends, seq_x)], -1)
         carry = start_hiddens
         outs = []
         for t in range(seq_x.shape[0]):
