@@ -904,6 +904,106 @@ int mlearn_layernorm_bwd(const void* x, int64_t ldx, int32_t dtype, const float*
                          mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Discrete PPO actor objective (dists.py:54-77 action_stats with the      */
+/* surrogate and entropy terms of ppo.py:145-239); the torch path's actor  */
+/* loss (additive exports)                                                 */
+/* ---------------------------------------------------------------------- */
+/* Per row r and sub-action k (group k of `layout`, logits l_j upcast to f32,
+ * p = softmax(l), a the action clamped into the group):
+ *   logp = l_a - logsumexp(l), H = -sum_j p_j log p_j,
+ *   A^ = adv[r], or (adv[r] - adv_stats[0]) adv_stats[1] with adv_stats,
+ *   rho = exp(logp - old_logp), c = min(max(rho, clip_lo), clip_hi),
+ *   obj = min(A^ rho, A^ c);
+ *   terms[0] = sum_k obj_coef[k] sum_r w_r obj[r][k] / rows,
+ *   terms[1] = sum_k ent_coef[k] sum_r w_r H[r][k] / rows,
+ * w_r = seq_weights[r mod M] (rows time-major [T][M]), 1 where seq_weights is
+ * NULL (M is then not read).  For the per-group means of the PPO loss,
+ * obj_coef[k] = 1 / K_g and ent_coef[k] = c_g / K_g, g the configured group of
+ * K_g sub-actions holding k and c_g its entropy coefficient.
+ * logits: [rows][num_logits] in `dtype` (f32 or bf16) with unit column stride,
+ * a row stride ld >= num_logits in elements and any base alignment: where
+ * the base is 16-byte aligned and the row stride a multiple of 16 bytes the
+ * rows move as 16-byte accesses, elsewhere element by element, with the same
+ * bits.  actions int32, old_logp, logp, ent, obj f32: contiguous [rows][K]
+ * (obj and ent unweighted); adv f32 [rows]; adv_stats f32 [2], seq_weights f32
+ * [M], g_terms and terms f32 [2], all device memory read by the kernels (no
+ * host read: the calls record into a HIP graph).  Layouts: 1..16 groups of >= 1
+ * logit, at most 95 logits.  Anything else (a null required pointer, rows < 1,
+ * a row stride below num_logits, another dtype, an empty group, offsets that do
+ * not span num_logits, seq_weights with M < 1, clip_lo > clip_hi or not finite)
+ * is MLEARN_EINVAL before the device is touched.  Nothing is allocated, no host
+ * synchronisation, no atomics. */
+typedef struct mlearn_actor_obj_coefs {
+    float clip_lo, clip_hi;              /* 1 - clip_coef, 1 + clip_coef as the caller rounds them */
+    float obj_coef[MLEARN_MAX_GROUPS];   /* per sub-action */
+    float ent_coef[MLEARN_MAX_GROUPS];
+} mlearn_actor_obj_coefs;
+
+/* Bytes of the forward's workspace (pure host): one [2] f32 row per workgroup,
+ * at most 1024 of them; negative for rows < 1. */
+int64_t mlearn_actor_obj_workspace_bytes(int64_t rows);
+/* logp, ent, obj and terms.  Each workgroup sums a fixed, contiguous share of
+ * the rows into its row of `workspace` (4-byte aligned) and a second launch
+ * adds those rows in a fixed order (in f64): terms depends on the inputs and
+ * `rows` only, the same bits on every call and every graph replay. */
+int mlearn_actor_obj_fwd(const void* logits, int64_t ld, int32_t dtype, mlearn_action_layout layout,
+                         int64_t rows, int64_t M, const int32_t* actions, const float* old_logp,
+                         const float* adv, const float* adv_stats, const float* seq_weights,
+                         const mlearn_actor_obj_coefs* coefs, float* logp, float* ent, float* obj,
+                         float* terms, void* workspace, mlearn_stream_t stream);
+/* d (g_terms . terms) / d logits, recomputed from the same inputs (the forward
+ * saves nothing else).  With s1 = A^ rho, s2 = A^ c:
+ *   m = 1 where s1 < s2, 1/2 where equal, else 0;
+ *   dc = 1 where clip_lo < rho < clip_hi, 1/2 at either end, else 0
+ *   (minimum / maximum split their gradient evenly at a tie);
+ *   dobj = s1 (m + (1 - m) dc)  (= A^ on-policy, rho = 1);
+ *   d l_j = g_terms[0] obj_coef[k] (w_r / rows) dobj ([j = a] - p_j)
+ *         - g_terms[1] ent_coef[k] (w_r / rows) p_j (log p_j + H).
+ * d_logits in `dtype` with row stride ld_d >= num_logits, each element rounded
+ * once; columns past num_logits are not written. */
+int mlearn_actor_obj_bwd(const void* logits, int64_t ld, int32_t dtype, mlearn_action_layout layout,
+                         int64_t rows, int64_t M, const int32_t* actions, const float* old_logp,
+                         const float* adv, const float* adv_stats, const float* seq_weights,
+                         const mlearn_actor_obj_coefs* coefs, const float* g_terms, void* d_logits,
+                         int64_t ld_d, mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
+/* Two-hot critic head (dists.py:119-208 SymExpTwoHotDistribution, the     */
+/* critic of DreamerV3Critic); the torch path's critic statistics          */
+/* (additive exports)                                                      */
+/* ---------------------------------------------------------------------- */
+/* One head of num_bins logits, num_bins odd within 3..255; bins_j =
+ * symexp(linspace(-14, 0, num_bins / 2 + 1)) mirrored (dists.py:128-141),
+ * formed in the kernel.  With p = softmax(logits):
+ *   mean = p_mid bins_mid + sum_i (p_{mid-1-i} bins_{mid-1-i} + p_{mid+1+i}
+ *          bins_{mid+1+i})  (exactly 0 at zero logits);
+ *   loss = -sum_j twohot_j log p_j, twohot the reference's weights on the two
+ *          bins around the target (1/2 each where the clipped indices coincide).
+ * Logits: [R][num_bins] in `dtype` (f32 or bf16, upcast to f32) with a row
+ * stride ld >= num_bins in elements, any base alignment.  targets, loss, mean
+ * and the incoming gradients are contiguous f32 [R].  Bad arguments (a bin
+ * count that is even or outside 3..255, a null required pointer, ld below the
+ * bin count, another dtype, R < 0) are MLEARN_EINVAL before any pointer is
+ * followed or the device is touched; R == 0 succeeds and launches nothing.
+ * One launch each on `stream`, nothing allocated, no host synchronisation, no
+ * atomics; every output element has one writer and a row's results do not
+ * depend on R or on the other rows. */
+int mlearn_twohot_mean(const void* logits, int64_t ld, int32_t dtype, int32_t num_bins, int64_t R,
+                       float* mean, mlearn_stream_t stream);
+/* two_hot_cross_entropy_loss(targets) and, where mean is not NULL, mean(). */
+int mlearn_twohot_loss(const void* logits, int64_t ld, int32_t dtype, int32_t num_bins,
+                       const float* targets, int64_t R, float* loss, float* mean,
+                       mlearn_stream_t stream);
+/* Their gradient, recomputed from the logits and targets:
+ *   d_j = g_loss (sum(twohot) p_j - twohot_j) + g_mean p_j (bins_j - mean).
+ * g_loss / g_mean may be NULL (zero).  d_logits in `dtype` with row stride
+ * ld_d >= num_bins, each element rounded once; columns past num_bins are not
+ * written. */
+int mlearn_twohot_loss_bwd(const void* logits, int64_t ld, int32_t dtype, int32_t num_bins,
+                           const float* targets, const float* g_loss, const float* g_mean,
+                           void* d_logits, int64_t ld_d, int64_t R, mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* LSTM sequence (rnn.py MultiLayerLSTMCell / LSTM.sequence): the          */
 /* recurrent part of one layer over a BPTT chunk on the torch path         */
 /* (additive exports)                                                      */

@@ -43,6 +43,11 @@ class HLGaussTables(Structure):  # mlearn_hlgauss_tables
                 ("centers", c_void_p * 2), ("bounds", c_void_p * 2)]
 
 
+class ActorObjCoefs(Structure):  # mlearn_actor_obj_coefs
+    _fields_ = [("clip_lo", c_float), ("clip_hi", c_float), ("obj_coef", c_float * MAX_GROUPS),
+                ("ent_coef", c_float * MAX_GROUPS)]
+
+
 class MlpPolicy(Structure):
     _fields_ = [("dtype", c_int32), ("obs_dim", c_int32), ("hidden", c_int32),
                 ("num_layers", c_int32), ("critic_bins", c_int32), ("actions", ActionLayout),
@@ -284,6 +289,16 @@ _SIGNATURES = {
                                        c_int32, _P, c_int64, _P, _P, _S]),
     "mlearn_layernorm_bwd": (c_int32, [_P, c_int64, c_int32, _P, _P, _P, _P, _P, c_int64, c_int64,
                                        c_int32, c_int32, _P, c_int64, _P, _P, _P, _S]),
+    "mlearn_actor_obj_workspace_bytes": (c_int64, [c_int64]),
+    "mlearn_actor_obj_fwd": (c_int32, [_P, c_int64, c_int32, ActionLayout, c_int64, c_int64, _P, _P,
+                                       _P, _P, _P, POINTER(ActorObjCoefs), _P, _P, _P, _P, _P,
+                                       _S]),
+    "mlearn_actor_obj_bwd": (c_int32, [_P, c_int64, c_int32, ActionLayout, c_int64, c_int64, _P, _P,
+                                       _P, _P, _P, POINTER(ActorObjCoefs), _P, _P, c_int64, _S]),
+    "mlearn_twohot_mean": (c_int32, [_P, c_int64, c_int32, c_int32, c_int64, _P, _S]),
+    "mlearn_twohot_loss": (c_int32, [_P, c_int64, c_int32, c_int32, _P, c_int64, _P, _P, _S]),
+    "mlearn_twohot_loss_bwd": (c_int32, [_P, c_int64, c_int32, c_int32, _P, _P, _P, _P, c_int64,
+                                         c_int64, _S]),
     "mlearn_lstm_seq_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32]),
     "mlearn_lstm_seq_fwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
                                       _P, _P, _P, _P, _P, _S]),

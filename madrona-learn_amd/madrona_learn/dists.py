@@ -248,25 +248,99 @@ def _symexp(x):  # utils.py:39-40
     return torch.sign(x) * torch.expm1(torch.abs(x))
 
 
-class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
-    """Torch form for trees outside the fused path; the fused kernels compute
-    the same mean() / two-hot cross entropy in csrc/dists.h."""
+def _th_rows(x):
+    """Raw logits [..., nb] as a [R, nb] view with unit column stride in a
+    dtype the kernels read (a copy only where no such view exists)."""
+    if x.dtype not in (torch.float32, torch.bfloat16):
+        x = x.float()
+    nb = x.shape[-1]
+    x = x.reshape(-1, nb)
+    if x.stride(1) != 1 or (x.shape[0] > 1 and x.stride(0) < nb):
+        x = x.contiguous()
+    return x, (x.stride(0) if x.shape[0] > 1 else nb)
 
-    def __init__(self, logits):
-        self.logits = logits.float()
+
+class _TwoHotLoss(torch.autograd.Function):
+    """two_hot_cross_entropy_loss and mean() on mlearn_twohot_loss, the
+    gradient on mlearn_twohot_loss_bwd (recomputed from the logits and the
+    targets: nothing else is saved).  logits: a [R, nb] view of _th_rows."""
 
     @staticmethod
-    def create(logits):
-        return SymExpTwoHotDistribution(logits)
+    def forward(ctx, targets, logits):
+        R, nb = logits.shape
+        tgt = targets.to(torch.float32).reshape(R).contiguous()
+        loss = torch.empty(R, dtype=torch.float32, device=logits.device)
+        mean = torch.empty_like(loss)
+        ld = logits.stride(0) if R > 1 else nb
+        if R:
+            nat.check(nat.lib().mlearn_twohot_loss(
+                logits.data_ptr(), ld, nat.dtype_code(logits.dtype), nb, nat.ptr(tgt), R,
+                nat.ptr(loss), nat.ptr(mean), nat.stream_handle()), "twohot_loss")
+        ctx.save_for_backward(tgt, logits)
+        ctx.set_materialize_grads(False)
+        return loss, mean
+
+    @staticmethod
+    def backward(ctx, g_loss, g_mean):
+        tgt, logits = ctx.saved_tensors
+        R, nb = logits.shape
+        g_loss = None if g_loss is None else g_loss.to(torch.float32).contiguous()
+        g_mean = None if g_mean is None else g_mean.to(torch.float32).contiguous()
+        d = torch.empty((R, nb), dtype=logits.dtype, device=logits.device)
+        if R:
+            nat.check(nat.lib().mlearn_twohot_loss_bwd(
+                logits.data_ptr(), logits.stride(0) if R > 1 else nb, nat.dtype_code(logits.dtype),
+                nb, nat.ptr(tgt), nat.ptr(g_loss), nat.ptr(g_mean), nat.ptr(d), nb, R,
+                nat.stream_handle()), "twohot_loss_bwd")
+        return None, d
+
+
+class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
+    """The torch path's implementation; the fused kernels compute the same
+    mean() / two-hot cross entropy in csrc/dists.h.
+
+    ``kernel``: None / 0 / "torch" evaluate the torch composition (also what
+    CPU tensors get); "hip" runs the HIP kernels of csrc/twohot.hip on GPU
+    tensors (odd bin counts within 3..255), which read the logits in their own
+    dtype (f32 / bf16) and row stride: no f32 copy is made on that path
+    (``.logits`` still returns f32 to other readers)."""
+
+    kernel = 0  # the default of instances created without kernel=
+
+    def __init__(self, logits, kernel=None):
+        self._raw = logits
+        self._f32 = None
+        if kernel is not None:
+            self.kernel = _kernel_choice(kernel)
+
+    @property
+    def logits(self):  # dists.py:122 upcasts to f32
+        if self._f32 is None:
+            self._f32 = self._raw.float()
+        return self._f32
+
+    @staticmethod
+    def create(logits, kernel=None):
+        return SymExpTwoHotDistribution(logits, kernel=kernel)
+
+    def _hip(self):
+        if self.kernel != "hip":
+            return False
+        nb = self._raw.shape[-1]
+        if not self._raw.is_cuda or nb % 2 == 0 or not 3 <= nb <= 255:
+            raise NotImplementedError(
+                f"SymExpTwoHotDistribution: kernel='hip' needs GPU tensors and an odd bin count "
+                f"within 3..255 (got {self._raw.device}, {nb} bins)")
+        return True
 
     def _compute_bins(self):
-        nb = self.logits.shape[-1]
+        nb = self._raw.shape[-1]
         assert nb % 2 == 1 and nb > 1
         half = _symexp(torch.linspace(-14, 0, nb // 2 + 1, dtype=torch.float32,
-                                      device=self.logits.device))
+                                      device=self._raw.device))
         return torch.cat([half, -torch.flip(half[:-1], [0])])
 
-    def mean(self):
+    def _mean_torch(self):
         bins = self._compute_bins()
         mid = (bins.shape[-1] - 1) // 2
         p = torch.softmax(self.logits, -1)
@@ -275,7 +349,7 @@ class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
         return (p[..., mid:mid + 1] * bins[mid:mid + 1]).sum(-1, keepdim=True) + \
             (lo + hi).sum(-1, keepdim=True)
 
-    def two_hot_cross_entropy_loss(self, targets):
+    def _loss_torch(self, targets):
         bins = self._compute_bins()
         nb = bins.shape[-1]
         t = targets.float()
@@ -291,8 +365,42 @@ class SymExpTwoHotDistribution:  # dists.py:119-208 (critic of DreamerV3Critic)
         logp = self.logits - torch.logsumexp(self.logits, -1, keepdim=True)
         return -(two_hot * logp).sum(-1, keepdim=True)
 
+    def _loss_and_mean_hip(self, targets):
+        lead = self._raw.shape[:-1]
+        loss, mean = _TwoHotLoss.apply(targets, _th_rows(self._raw)[0])
+        return loss.reshape(*lead, 1), mean.reshape(*lead, 1)
+
+    def mean(self):
+        if not self._hip():
+            return self._mean_torch()
+        lead = self._raw.shape[:-1]
+        if torch.is_grad_enabled() and self._raw.requires_grad:
+            # through _TwoHotLoss where a gradient may be asked for (the torch
+            # mean() is differentiable)
+            zeros = torch.zeros(lead, dtype=torch.float32, device=self._raw.device)
+            return self._loss_and_mean_hip(zeros)[1]
+        lg, ld = _th_rows(self._raw.detach())
+        R, nb = lg.shape
+        mean = torch.empty(R, dtype=torch.float32, device=lg.device)
+        if R:
+            nat.check(nat.lib().mlearn_twohot_mean(lg.data_ptr(), ld, nat.dtype_code(lg.dtype), nb,
+                                                   R, nat.ptr(mean), nat.stream_handle()),
+                      "twohot_mean")
+        return mean.reshape(*lead, 1)
+
+    def two_hot_cross_entropy_loss(self, targets):
+        return self._loss_and_mean_hip(targets)[0] if self._hip() else self._loss_torch(targets)
+
+    def loss_and_mean(self, targets):
+        """(two_hot_cross_entropy_loss(targets), mean()), each [..., 1]: one
+        launch on the kernels."""
+        if self._hip():
+            return self._loss_and_mean_hip(targets)
+        return self._loss_torch(targets), self._mean_torch()
+
     def reshape(self, *shape):
-        return SymExpTwoHotDistribution(self.logits.reshape(*shape, self.logits.shape[-1]))
+        return SymExpTwoHotDistribution(self._raw.reshape(*shape, self._raw.shape[-1]),
+                                        kernel=self.kernel)
 
 
 def _hl_tables(parts):

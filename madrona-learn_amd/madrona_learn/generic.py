@@ -19,7 +19,8 @@ autograd, while everything around them stays on the HIP kernels of
   (mlearn_minibatch_perm) and the per-minibatch advantage statistics of
   ``zscore_data`` (mlearn_adv_stats / _finish, all-reduced under DP);
 * ``action_stats`` (mlearn_action_stats_f32 forward; its backward through
-  the softmax in torch);
+  the softmax in torch), or with ``TorchPPO.actor_kernel = 2`` the whole
+  discrete actor objective and its gradient (mlearn_actor_obj_fwd / _bwd);
 * continuous actions (``TrainConfig.actions`` of ContinuousActionsConfig, an
   actor returning ``ContinuousActionDistributions``): Box-Muller sampling over
   the Philox counter stream (mlearn_continuous_sample) and the distribution's
@@ -57,6 +58,8 @@ import torch
 from torch import nn
 
 from . import _native as nat
+from .actor_obj import actor_objective
+from .actor_obj import coefs as actor_obj_coefs
 from .dists import (DiscreteActionDistributions, HLGaussDist, HLGaussTwoPartDist, PhiloxKey,
                     SymExpTwoHotDistribution)
 from .dynamic_scale import DynamicScale
@@ -559,7 +562,14 @@ class TorchPPO(PPO):
     permutation and per-minibatch advantage statistics (HIP, all-reduced
     under DP), then per minibatch the loss of ppo.py:129-262 under torch
     autograd over ActorCritic.update, the gradient all-reduce, and the flat
-    HIP optimizer step."""
+    HIP optimizer step.
+
+    actor_kernel (class attribute, as PPO.step_kernel): the discrete actor's
+    objective (actor_obj.py), 0 = the library's choice, 1 = the torch
+    composition, 2 = the HIP kernels of csrc/actor_obj.hip
+    (NotImplementedError where they do not apply: continuous groups, fp16)."""
+
+    actor_kernel = 0
 
     def prepare(self, cfg, ps, ts, view, dp, store, col0=0, policy_idx=0):
         """``store``: the RolloutManager's store; ``col0``: this policy's first
@@ -593,6 +603,8 @@ class TorchPPO(PPO):
         ec = algo.entropy_coef
         self.ecoef = [float(_base(ec[n] if isinstance(ec, dict) else ec)) for n, _ in self.groups]
         self.clip = float(algo.clip_coef)
+        self.obj_coefs = None if self.cont is not None else \
+            actor_obj_coefs(self.groups, self.ecoef, self.clip)
         self.vcoef = float(algo.value_loss_coef)
         self.clip_vl = bool(algo.clip_value_loss)
         self.huber = bool(algo.huber_value_loss)
@@ -645,45 +657,16 @@ class TorchPPO(PPO):
                                                 mbd["dones"][..., None], obs, train=True)
         dists = act_f(feats_a, train=True) if _takes_train(act_f) else act_f(feats_a)
         crit = ac.critic(feats_c, train=True) if _takes_train(ac.critic) else ac.critic(feats_c)
-        if self.cont is not None:
-            # the distribution's own differentiable action_stats, per dimension
-            # (dists.py:260-284): [T, M, G, D] -> the G D stored columns; the
-            # ratio, clip and min below are per column, the advantage broadcast
-            # over them (ppo.py:145-164)
-            logp, ent = dists.action_stats(mbd["actions"].reshape(dists.means.shape))
-        else:
-            logp, ent = action_stats_autograd(dists, mbd["actions"].reshape(T * M, -1))
-        K = logp.numel() // (T * M)
-        logp = logp.reshape(T, M, K)
-        ent = ent.reshape(T, M, K)
-        adv = mbd["advantages"].float()
-        if self.norm_adv:
-            adv = (adv - adv_stats[0]) * adv_stats[1]  # zscore_data with the minibatch's stats
-        ratio = torch.exp(logp - mbd["log_probs"])
-        a = adv[..., None]
-        surr1 = a * ratio
-        # jnp.clip = minimum(maximum(x, lo), hi): 0.5 derivatives at ties
-        lo = torch.full_like(ratio, 1.0 - self.clip)
-        hi = torch.full_like(ratio, 1.0 + self.clip)
-        surr2 = a * torch.minimum(torch.maximum(ratio, lo), hi)
-        obj = torch.minimum(surr1, surr2)
+        # log-probs, entropies, the clipped surrogate and the per-group means
+        # (actor_obj.py: the torch composition or the HIP kernels)
+        action_obj, entropy_term, obj, ent = actor_objective(
+            type(self).actor_kernel, dists, mbd["actions"], mbd["log_probs"], mbd["advantages"],
+            adv_stats if self.norm_adv else None, weights, self.groups, self.ecoef, self.clip,
+            self.cont, self.obj_coefs)
         w3 = None if weights is None else weights.reshape(1, M, 1)
-        obj_w = obj if w3 is None else w3 * obj
-        ent_w = ent if w3 is None else w3 * ent
-        action_obj = 0.0
-        entropy_term = 0.0
-        off = 0
-        for grp, c in zip(self.groups, self.ecoef):
-            k = grp.cols
-            action_obj = action_obj + obj_w[..., off:off + k].mean()
-            entropy_term = entropy_term + c * ent_w[..., off:off + k].mean()
-            off += k
         R = mbd["returns"].float()
         verr = None
-        if isinstance(crit, SymExpTwoHotDistribution):
-            vl = crit.two_hot_cross_entropy_loss(R.reshape(-1, 1)).reshape(T, M)
-            V = crit.mean().reshape(T, M)
-        elif isinstance(crit, _HLGAUSS):  # ppo.py:178-185
+        if isinstance(crit, (SymExpTwoHotDistribution,) + _HLGAUSS):  # ppo.py:170-185
             vl, V = crit.loss_and_mean(R.reshape(-1, 1))
             vl, V = vl.reshape(T, M), V.reshape(T, M)
         else:

@@ -390,16 +390,20 @@ class DenseLayerCritic(nn.Module):  # models.py:142-154 (output cast to f32)
 
 
 class DreamerV3Critic(nn.Module):  # models.py:157-174 (SymExpTwoHotDistribution head)
-    def __init__(self, dtype, weight_init=constant(0.0), num_bins=63):
+    """kernel: SymExpTwoHotDistribution's switch (None: its default, the torch
+    composition; "hip": the kernels of csrc/twohot.hip)."""
+
+    def __init__(self, dtype, weight_init=constant(0.0), num_bins=63, kernel=None):
         super().__init__()
         self.dtype = canonical_dtype(dtype)
+        self.kernel = kernel
         self.weight_init = weight_init
         self.num_bins = num_bins
         self.impl = _Dense(num_bins, True, self.dtype, weight_init)
 
     def forward(self, features, train=False):
         from .dists import SymExpTwoHotDistribution
-        return SymExpTwoHotDistribution(self.impl(features))
+        return SymExpTwoHotDistribution(self.impl(features), kernel=self.kernel)
 
 
 class HLGaussCritic(nn.Module):  # models.py:253-307 (HLGaussDist head)
