@@ -904,6 +904,56 @@ int mlearn_layernorm_bwd(const void* x, int64_t ldx, int32_t dtype, const float*
                          mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Dense + LayerNorm + activation (models.py:99-119 MLP, 463-478 the entity */
+/* encoder's embed and ff_0 / ff_norm): one trunk layer of the torch path   */
+/* as one kernel (additive exports)                                         */
+/* ---------------------------------------------------------------------- */
+/* y = act(LN(x w)): x [rows][in_features] contiguous in `dtype`
+ * (MLEARN_DTYPE_F32 / MLEARN_DTYPE_BF16, any element-aligned base: 16-byte
+ * row fragments where the base is 16-byte aligned and in_features a multiple
+ * of 16 bytes of elements, element by element elsewhere; no byte past a row's
+ * in_features columns is read), w the f32 parameter [in_features][features]
+ * (cast to `dtype` for the product, f32 accumulation), scale, bias f32
+ * [features].  The LayerNorm is mlearn_layernorm_fwd's on the unrounded f32
+ * product (eps 1e-6), with its rounding points: the normalised value rounded
+ * to `dtype`, the activation (0: none, 1: ReLU, 2: leaky ReLU of slope 0.01)
+ * on the rounded value, rounded again.  y [rows][features] contiguous in
+ * `dtype`, 16-byte aligned; mean, rstd f32 [rows].  features: a multiple of
+ * 32 up to 256; in_features 1..512; rows >= 1.  `workspace` (16-byte aligned,
+ * workspace_bytes >= mlearn_dense_ln_workspace_bytes) receives the weight
+ * images, laid by a launch of each call.  Anything else (a null pointer,
+ * another dtype or act, a misaligned y, a too-small workspace) is
+ * MLEARN_EINVAL before the device is touched.  Nothing is allocated, no host
+ * synchronisation, no atomics. */
+int mlearn_dense_ln_fwd(const void* x, const float* w, const float* scale, const float* bias,
+                        int64_t rows, int32_t in_features, int32_t features, int32_t dtype,
+                        int32_t act, void* y, float* mean, float* rstd, void* workspace,
+                        int64_t workspace_bytes, mlearn_stream_t stream);
+/* Bytes of the workspace of both calls (pure host, an upper bound for every
+ * device): the two weight images and at most 512 [2][features] f32 partial
+ * rows; negative where the kernels do not apply. */
+int64_t mlearn_dense_ln_workspace_bytes(int64_t rows, int32_t in_features, int32_t features,
+                                        int32_t dtype);
+/* The gradient.  z = x w is recomputed with the forward's product (the same
+ * bits), x_hat and the mask (the sign of the rounded LayerNorm output) from it:
+ *   g = dy act'(.), v = g scale,
+ *   dz = rstd (v - mean_F(v) - x_hat mean_F(v x_hat)), rounded to `dtype`,
+ *   dx = dz w^T from the rounded dz (f32 accumulation, rounded once),
+ *   dbias = sum_rows g, dscale = sum_rows g x_hat.
+ * dy, dz [rows][features] contiguous in `dtype`, 16-byte aligned (dz is the
+ * operand of the caller's weight gradient dw = x^T dz); dx [rows][in_features]
+ * contiguous in `dtype`, or null: the product is skipped.  dscale and dbias:
+ * each workgroup sums a contiguous share of the row tiles into one partial
+ * row of the workspace and a second launch adds the rows in index order, so
+ * they depend on (rows, the device's CU count) only, the same bits on every
+ * call. */
+int mlearn_dense_ln_bwd(const void* x, const float* w, const float* scale, const float* bias,
+                        const float* mean, const float* rstd, const void* dy, int64_t rows,
+                        int32_t in_features, int32_t features, int32_t dtype, int32_t act,
+                        void* dz, void* dx, float* dscale, float* dbias, void* workspace,
+                        int64_t workspace_bytes, mlearn_stream_t stream);
+
+/* ---------------------------------------------------------------------- */
 /* Discrete PPO actor objective (dists.py:54-77 action_stats with the      */
 /* surrogate and entropy terms of ppo.py:145-239); the torch path's actor  */
 /* loss (additive exports)                                                 */

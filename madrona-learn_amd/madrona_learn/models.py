@@ -20,6 +20,7 @@ import torch
 from torch import nn
 
 from . import attention as _attention
+from . import dense_ln as _dense_ln
 from . import layernorm as _layernorm
 from .cfg import ContinuousActionsConfig, DiscreteActionsConfig, canonical_dtype
 
@@ -83,12 +84,15 @@ class _Dense(nn.Module):
         self.kernel = None
         self.bias = None
 
-    def forward(self, x):
+    def materialize(self, x):
         if self.kernel is None:
             w = self.kernel_init(_init_rng(), (x.shape[-1], self.features))
             self.kernel = nn.Parameter(torch.from_numpy(np.asarray(w, np.float32)).to(x.device))
             if self.use_bias:
                 self.bias = nn.Parameter(torch.zeros(self.features, device=x.device))
+
+    def forward(self, x):
+        self.materialize(x)
         y = x.to(self.dtype) @ self.kernel.to(self.dtype)
         if self.use_bias:
             y = y + self.bias.to(self.dtype)
@@ -115,16 +119,42 @@ class LayerNorm(nn.Module):  # models.py:46-56 (flax nn.LayerNorm: eps 1e-6, f32
         self.scale = None
         self.bias = None
 
-    def forward(self, x, act=None):
-        F = x.shape[-1]
+    def materialize(self, F, device):
         if self.scale is None:
-            self.scale = nn.Parameter(torch.ones(F, device=x.device))
-            self.bias = nn.Parameter(torch.zeros(F, device=x.device))
+            self.scale = nn.Parameter(torch.ones(F, device=device))
+            self.bias = nn.Parameter(torch.zeros(F, device=device))
+
+    def forward(self, x, act=None):
+        self.materialize(x.shape[-1], x.device)
         kernel = type(self).layer_norm_kernel if self.kernel is None else self.kernel
         return _layernorm.layer_norm(x, self.scale, self.bias, self.dtype, act, kernel)
 
 
+def _dense_norm(dense, norm, x, act, which):
+    """One Dense (no bias) -> LayerNorm -> activation layer of a trunk under
+    the selector `which` of MLP.layer_kernel: 0 = the library's choice
+    (dense_ln._default_is_hip), 1 = the two modules one after the other, 2 =
+    the fused HIP kernels of csrc/dense_ln.hip (NotImplementedError where they
+    do not apply: CPU tensors, fp16, an input of another dtype than the
+    module's, features that are no multiple of 32 or above 256, more than 512
+    input features).  Parameters are created in the two modules' order:
+    dense.kernel, then norm.scale and norm.bias."""
+    if which not in (0, 1, 2):
+        raise ValueError(f"layer_kernel {which}: 0 (library's choice), 1 (Dense then LayerNorm) "
+                         "or 2 (the fused HIP kernels)")
+    if which == 1 or (which == 0 and not _dense_ln.wants_hip(x, dense.features, dense.dtype)):
+        return norm(dense(x), act=act)
+    dense.materialize(x)
+    norm.materialize(dense.features, x.device)
+    return _dense_ln.dense_layer_norm_hip(x, dense.kernel, norm.scale, norm.bias, dense.dtype, act)
+
+
 class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU per layer
+    """layer_kernel (class attribute, as LayerNorm.layer_norm_kernel): how each
+    layer runs, see _dense_norm."""
+
+    layer_kernel = 0
+
     def __init__(self, num_channels, num_layers, dtype, weight_init=orthogonal(math.sqrt(2))):
         super().__init__()
         self.num_channels = int(num_channels)
@@ -138,7 +168,7 @@ class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU p
     def forward(self, inputs, train=False):
         x = inputs
         for d, n in zip(self.dense, self.norms):
-            x = n(d(x), act="relu")
+            x = _dense_norm(d, n, x, "relu", type(self).layer_kernel)
         return x
 
 
@@ -196,13 +226,18 @@ def _sorted_leaves(tree, out):
 
 
 class _EntityEmbed(nn.Module):  # models.py:463-478: Dense (no bias) -> LayerNorm -> leaky ReLU
+    """layer_kernel (class attribute): see _dense_norm; EntitySelfAttentionNet's
+    ff_0 / ff_norm pair takes the same selector."""
+
+    layer_kernel = 0
+
     def __init__(self, features, dtype, dense_init):
         super().__init__()
         self.dense = _Dense(features, False, dtype, dense_init)
         self.norm = LayerNorm(dtype)
 
     def forward(self, x):
-        return self.norm(self.dense(x), act="leaky_relu")
+        return _dense_norm(self.dense, self.norm, x, "leaky_relu", type(self).layer_kernel)
 
 
 class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use entity encoder)
@@ -259,7 +294,7 @@ class EntitySelfAttentionNet(nn.Module):  # models.py:451-540 (Emergent Tool Use
             attended = attended + embedded
         attended = self.attended_norm(attended.mean(dim=-2))
 
-        ff = self.ff_norm(self.ff_0(attended), act="leaky_relu")
+        ff = _dense_norm(self.ff_0, self.ff_norm, attended, "leaky_relu", _EntityEmbed.layer_kernel)
         ff = nn.functional.leaky_relu(self.ff_1(ff))  # (a transformer block has no activation here)
         return self.out_norm(attended + ff)
 
