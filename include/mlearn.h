@@ -954,6 +954,36 @@ int mlearn_dense_ln_bwd(const void* x, const float* w, const float* scale, const
                         int64_t workspace_bytes, mlearn_stream_t stream);
 
 /* ---------------------------------------------------------------------- */
+/* Tall-skinny weight gradient: the dW = x^T dy (and db) of the torch      */
+/* path's Dense layers, very many rows and a small output (additive        */
+/* exports)                                                                 */
+/* ---------------------------------------------------------------------- */
+/* dw[k][f] = sum_r x[r][k] dy[r][f] and, where db is not null, db[f] =
+ * sum_r dy[r][f].  x [rows][in_features] and dy [rows][features] contiguous in
+ * `dtype` (MLEARN_DTYPE_F32 / MLEARN_DTYPE_BF16, any element-aligned bases: an
+ * operand moves in 16-byte pieces where its base is 16-byte aligned and its
+ * width a multiple of 16 bytes of elements, element by element elsewhere; no
+ * byte outside a row or past the last row is read); dw [in_features][features]
+ * and db [features] f32.  in_features 1..512, features 1..256, rows >= 1.  The
+ * products are the MFMA's (bf16 x bf16 or exact f32), accumulated in f32; the
+ * inputs are never rounded.  Each workgroup sums one contiguous share of the
+ * rows into one f32 slab of `workspace` (16-byte aligned, workspace_bytes >=
+ * mlearn_skinny_wgrad_workspace_bytes) and a second launch adds the slabs in a
+ * fixed order: the result depends on (the inputs, the device's CU count) only,
+ * the same bits on every call and under graph replay.  Anything else (a null
+ * pointer other than db, another dtype, a range, a misaligned pointer, a
+ * too-small workspace) is MLEARN_EINVAL before the device is touched.  Nothing
+ * is allocated, no host synchronisation, no atomics. */
+int mlearn_skinny_wgrad(const void* x, const void* dy, int64_t rows, int32_t in_features,
+                        int32_t features, int32_t dtype, float* dw, float* db, void* workspace,
+                        int64_t workspace_bytes, mlearn_stream_t stream);
+/* Bytes of that workspace (pure host, an upper bound for every device): at
+ * most 1024 slabs of in_features x features + features floats; -1 where the
+ * kernel does not apply. */
+int64_t mlearn_skinny_wgrad_workspace_bytes(int64_t rows, int32_t in_features, int32_t features,
+                                            int32_t dtype);
+
+/* ---------------------------------------------------------------------- */
 /* Discrete PPO actor objective (dists.py:54-77 action_stats with the      */
 /* surrogate and entropy terms of ppo.py:145-239); the torch path's actor  */
 /* loss (additive exports)                                                 */

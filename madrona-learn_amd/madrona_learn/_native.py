@@ -294,6 +294,9 @@ _SIGNATURES = {
                                       _P, _P, _P, _P, c_int64, _S]),
     "mlearn_dense_ln_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, _P, c_int64, c_int32, c_int32,
                                       c_int32, c_int32, _P, _P, _P, _P, _P, c_int64, _S]),
+    "mlearn_skinny_wgrad_workspace_bytes": (c_int64, [c_int64, c_int32, c_int32, c_int32]),
+    "mlearn_skinny_wgrad": (c_int32, [_P, _P, c_int64, c_int32, c_int32, c_int32, _P, _P, _P,
+                                      c_int64, _S]),
     "mlearn_actor_obj_workspace_bytes": (c_int64, [c_int64]),
     "mlearn_actor_obj_fwd": (c_int32, [_P, c_int64, c_int32, ActionLayout, c_int64, c_int64, _P, _P,
                                        _P, _P, _P, POINTER(ActorObjCoefs), _P, _P, _P, _P, _P,

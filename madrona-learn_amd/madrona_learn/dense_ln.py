@@ -22,6 +22,7 @@ import torch
 
 from . import _native as nat
 from . import layernorm as _layernorm
+from . import skinny_wgrad as _skinny_wgrad
 
 MAX_FEATURES = 256
 MAX_IN_FEATURES = 512
@@ -104,16 +105,17 @@ def dense_ln_bwd(x2, kernel, scale, bias, mean, rstd, dy2, act, need_dx=True, ou
 class _DenseLayerNorm(torch.autograd.Function):
     """mlearn_dense_ln_fwd with mlearn_dense_ln_bwd as its gradient.  x, the
     parameters and the rows' mean and rstd are kept for the backward, which
-    recomputes the product; the weight gradient x^T dz is one torch GEMM."""
+    recomputes the product; the weight gradient x^T dz is one torch GEMM or,
+    with wgrad 2, mlearn_skinny_wgrad's f32 result."""
 
     @staticmethod
-    def forward(ctx, x, kernel, scale, bias, act):
+    def forward(ctx, x, kernel, scale, bias, act, wgrad=1):
         K, F = kernel.shape
         x2 = x.reshape(-1, K).contiguous()
         kernel, scale, bias = _f32(kernel), _f32(scale), _f32(bias)
         y, mean, rstd = dense_ln_fwd(x2, kernel, scale, bias, act)
         ctx.save_for_backward(x2, kernel, scale, bias, mean, rstd)
-        ctx.act, ctx.x_shape = act, x.shape
+        ctx.act, ctx.x_shape, ctx.wgrad = act, x.shape, wgrad
         return y.view(*x.shape[:-1], F)
 
     @staticmethod
@@ -122,12 +124,20 @@ class _DenseLayerNorm(torch.autograd.Function):
         dy2 = dy.to(x2.dtype).reshape(-1, kernel.shape[1]).contiguous()
         dx, dz, dscale, dbias = dense_ln_bwd(x2, kernel, scale, bias, mean, rstd, dy2, ctx.act,
                                              ctx.needs_input_grad[0])
-        dw = (x2.t() @ dz).float()
-        return (dx.view(ctx.x_shape) if dx is not None else None), dw, dscale, dbias, None
+        if ctx.wgrad == 2:
+            dw = _skinny_wgrad.skinny_wgrad(x2, dz)[0]
+        else:
+            dw = (x2.t() @ dz).float()
+        return (dx.view(ctx.x_shape) if dx is not None else None), dw, dscale, dbias, None, None
 
 
-def dense_layer_norm_hip(x, kernel, scale, bias, dtype, act=None):
+def dense_layer_norm_hip(x, kernel, scale, bias, dtype, act=None, wgrad_kernel=0):
+    """wgrad_kernel: models._Dense.wgrad_kernel's selector for dw = x^T dz (the
+    fused kernels' range lies inside the weight-gradient kernel's)."""
     code = _layernorm._act_code(act)
+    if wgrad_kernel not in (0, 1, 2):
+        raise ValueError(f"wgrad_kernel {wgrad_kernel}: 0 (library's choice), 1 (the torch "
+                         "product) or 2 (the HIP weight-gradient kernel)")
     if x.dim() < 1 or kernel.dim() != 2 or x.shape[-1] != kernel.shape[0]:
         raise ValueError("dense_layer_norm: x's last dim is not the kernel's fan-in")
     why = hip_problem(x, kernel.shape[1], dtype)
@@ -135,7 +145,9 @@ def dense_layer_norm_hip(x, kernel, scale, bias, dtype, act=None):
         raise NotImplementedError(f"the HIP Dense + LayerNorm kernels do not take {why}")
     if scale.shape != (kernel.shape[1],) or bias.shape != scale.shape:
         raise ValueError("dense_layer_norm: scale and bias must hold one value per feature")
-    return _DenseLayerNorm.apply(x, kernel, scale, bias, code)
+    if wgrad_kernel == 0:
+        wgrad_kernel = 2 if _skinny_wgrad._default_is_hip(dtype, *kernel.shape) else 1
+    return _DenseLayerNorm.apply(x, kernel, scale, bias, code, wgrad_kernel)
 
 
 def _default_is_hip(dtype, in_features, features):

@@ -21,6 +21,7 @@ from torch import nn
 
 from . import attention as _attention
 from . import dense_ln as _dense_ln
+from . import skinny_wgrad as _skinny_wgrad
 from . import layernorm as _layernorm
 from .cfg import ContinuousActionsConfig, DiscreteActionsConfig, canonical_dtype
 
@@ -73,7 +74,16 @@ def _init_rng():
 
 
 class _Dense(nn.Module):
-    """flax nn.Dense with the given kernel init (bias init 0), created lazily."""
+    """flax nn.Dense with the given kernel init (bias init 0), created lazily.
+
+    wgrad_kernel (class attribute, as MLP.layer_kernel): where the weight (and
+    bias) gradient comes from, 0 = the library's choice
+    (skinny_wgrad._default_is_hip), 1 = torch autograd's products, 2 = the HIP
+    kernel of csrc/skinny_wgrad.hip (NotImplementedError where it does not
+    apply: CPU tensors, fp16, more than 512 inputs or 256 features); the
+    fused layers of _dense_norm take their weight gradient the same way."""
+
+    wgrad_kernel = 0
 
     def __init__(self, features, use_bias, dtype, kernel_init):
         super().__init__()
@@ -93,10 +103,8 @@ class _Dense(nn.Module):
 
     def forward(self, x):
         self.materialize(x)
-        y = x.to(self.dtype) @ self.kernel.to(self.dtype)
-        if self.use_bias:
-            y = y + self.bias.to(self.dtype)
-        return y
+        return _skinny_wgrad.dense(x, self.kernel, self.bias if self.use_bias else None,
+                                   self.dtype, type(self).wgrad_kernel)
 
 
 class LayerNorm(nn.Module):  # models.py:46-56 (flax nn.LayerNorm: eps 1e-6, f32 statistics)
@@ -146,7 +154,8 @@ def _dense_norm(dense, norm, x, act, which):
         return norm(dense(x), act=act)
     dense.materialize(x)
     norm.materialize(dense.features, x.device)
-    return _dense_ln.dense_layer_norm_hip(x, dense.kernel, norm.scale, norm.bias, dense.dtype, act)
+    return _dense_ln.dense_layer_norm_hip(x, dense.kernel, norm.scale, norm.bias, dense.dtype, act,
+                                          type(dense).wgrad_kernel)
 
 
 class MLP(nn.Module):  # models.py:99-119: Dense(no bias) -> LayerNorm -> ReLU per layer
