@@ -746,6 +746,25 @@ int mlearn_attention_bwd(const void* q, const void* k, const void* v, const void
                          int32_t seq, int32_t heads, int32_t head_dim, float scale,
                          void* dq, void* dk, void* dv, mlearn_stream_t stream);
 
+/* The same attention and gradient for seq 33..128 (additive exports;
+ * mlearn_attention_fwd / _bwd keep refusing seq > 32).  Arguments, layouts,
+ * the other domain limits, the argument checks (MLEARN_EINVAL before the
+ * device is touched) and the rounding contract are those of
+ * mlearn_attention_fwd / _bwd.  One workgroup of ceil(seq / 32) waves owns one
+ * (batch row, head): its operands are read from HBM once into LDS row images,
+ * every wave holds the whole score row of its 32 queries in registers (exact
+ * two-pass softmax), and in the gradient wave w writes dq of query tile w and
+ * dk, dv of key tile w: one writer per element, no atomics, identical bits on
+ * every call.  Up to 137 KiB of LDS per workgroup (f32, head_dim 64, seq > 96,
+ * gradient).  batch * heads < 2^31. */
+int mlearn_attention_long_fwd(const void* q, const void* k, const void* v, int32_t dtype,
+                              int64_t batch, int32_t seq, int32_t heads, int32_t head_dim,
+                              float scale, void* out, float* lse, mlearn_stream_t stream);
+int mlearn_attention_long_bwd(const void* q, const void* k, const void* v, const void* out,
+                              const float* lse, const void* dout, int32_t dtype, int64_t batch,
+                              int32_t seq, int32_t heads, int32_t head_dim, float scale,
+                              void* dq, void* dk, void* dv, mlearn_stream_t stream);
+
 /* The same attention with the mean over the query axis folded in (what
  * EntitySelfAttentionNet keeps of it; additive exports): per (batch row, head),
  * P = softmax(scale * q k^T) [seq x seq],

@@ -38,8 +38,12 @@
 // accumulation are f32, outputs are rounded once on store.  f32: the f32 MFMA
 // (a k-ordered fmaf chain), never through bf16.
 //
-// The pooled form (mean over the queries folded in, last part of this file)
-// keeps the fragments and tile forms and never forms O or a dO.
+// The pooled form (mean over the queries folded in) keeps the fragments and
+// tile forms and never forms O or a dO.
+//
+// The long form (seq 33..128, last kernels of this file) splits one problem
+// over the ceil(seq / 32) waves of a workgroup: NT x NT tiles of the same
+// forms, operands staged once in LDS, one writer per output row.
 #include <math.h>
 
 #include "common.h"
@@ -106,10 +110,11 @@ template <int D> struct RowFrag<float, D> {
 
 // Second level: Y^T[c][b] = sum_a Z[a][c] X[a][b] for the 32 channels
 // c = 32 tile + r of the LDS image z[a][LD]; channels >= D contribute zero rows.
+// c continues a chain over several 32-row blocks a (the long form below).
 template <int D, int LD>
-__device__ inline f32x16 acc_product(const bf16* z, const f32x16& x, int tile, int r, int h) {
+__device__ inline f32x16 acc_product(const bf16* z, const f32x16& x, int tile, int r, int h,
+                                     f32x16 c = {}) {
     const bool cv = 32 * tile + r < D;
-    f32x16 c = {};
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         bf16x8 fa, fb;
@@ -125,9 +130,9 @@ __device__ inline f32x16 acc_product(const bf16* z, const f32x16& x, int tile, i
 }
 
 template <int D, int LD>
-__device__ inline f32x16 acc_product(const float* z, const f32x16& x, int tile, int r, int h) {
+__device__ inline f32x16 acc_product(const float* z, const f32x16& x, int tile, int r, int h,
+                                     f32x16 c = {}) {
     const bool cv = 32 * tile + r < D;
-    f32x16 c = {};
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         const int a = (t & 3) + 8 * (t >> 2) + 4 * h;
@@ -903,18 +908,260 @@ __global__ __launch_bounds__(kAttnWaves* kWave) void attn_pooled_bwd16_kernel(
     F::product_store(z, ds, dk + ro, rv, scale, r, g);  // dK^T = scale q^T dS
 }
 
+// ---------------------------------------------------------------------------
+// Long form, seq 33..128: one workgroup of NT = ceil(seq / 32) waves owns one
+// (batch row, head) problem; the problem is NT x NT score tiles of the forms
+// above.  Wave w stages rows 32 w .. 32 w + 31 of every operand from HBM
+// (16-byte loads, once per workgroup) into row-major LDS images of 32 NT rows
+// (rows >= seq are zero rows), one __syncthreads, and from then on the waves
+// run independently:
+//   forward   wave w owns query tile w (its q rows never leave the registers):
+//       S^T_j = k_j q^T for every key tile j, k_j a first-level fragment read
+//       back from the k image with 16-byte LDS loads -> the whole score row of
+//       a query sits in the lane's 16 NT registers and those of the other lane
+//       half: an exact two-pass softmax, no online rescaling.  O^T = sum_j
+//       v_j^T P_j^T is one MFMA chain over the key tiles (acc_product with the
+//       accumulator carried) and is stored once.
+//   backward  D_i = dO_i . O_i of the wave's own rows as above (the diagonal of
+//       the dO O^T chain: dP - D sees one summation order); D and lse are
+//       shared through 2 x 32 NT floats of LDS at the staging barrier.
+//       As owner of key tile w (k_w, v_w in the registers) the wave loops over
+//       the query tiles i: P_iw, dS_iw with the query in the registers feed
+//       the chains dV_w^T += dO_i^T P_iw and dK_w^T += q_i^T dS_iw.  As owner
+//       of query tile w (q_w, dO_w in the registers) it loops over the key
+//       tiles j: dS_wj^T feeds dQ_w^T += k_j^T dS_wj^T.  Both orientations are
+//       recomputed; nothing is transposed through LDS.
+// Every output row has one writer and every sum one order: no atomics, no
+// cross-wave reduction, identical bits on every call.  LDS: 2 images in the
+// forward (k, v), 4 in the backward (q, k, v, dO): at most 68 KiB / 137 KiB
+// (f32, head_dim 64, NT 4), dynamic.
+// ---------------------------------------------------------------------------
+constexpr int kLongMaxSeq = 128;
+
+template <typename T, int D, int NT> struct LongGeo {
+    typedef Geo<T, D> G;
+    static constexpr int ROWS = 32 * NT;
+    static constexpr int IMG = ROWS * G::LD;  // elements of one row image (a multiple of 16 bytes)
+    static constexpr int FWD_LDS = 2 * IMG * (int)sizeof(T);
+    static constexpr int BWD_LDS = 4 * IMG * (int)sizeof(T) + 2 * ROWS * (int)sizeof(float);
+};
+
+template <typename T, int D, int NT>
+__global__ __launch_bounds__(NT* kWave) void attn_long_fwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v, T* __restrict__ out,
+    float* __restrict__ lse, int seq, int heads, float scale) {
+    typedef LongGeo<T, D, NT> L;
+    typedef typename L::G G;
+    typedef typename G::F F;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    T* zk = (T*)smem;
+    T* zv = zk + L::IMG;
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int64_t p = blockIdx.x;
+    const int64_t b = p / heads;
+    const int hd = (int)(p - b * heads);
+    const int row = 32 * w + r;  // this lane's query, and the row it stages
+    const bool rv = row < seq;
+    const int64_t ro = ((b * seq + row) * heads + hd) * D;  // (read and written only where rv)
+
+    F qf;
+    qf.load(q + ro, rv, h);
+    {
+        F xf;
+        xf.load(k + ro, rv, h);
+        xf.store_lds(zk + row * G::LD, h);
+        xf.load(v + ro, rv, h);
+        xf.store_lds(zv + row * G::LD, h);
+    }
+    __syncthreads();
+
+    // st[j][t] = S[query row][key 32 j + acc_row(t)]
+    f32x16 st[NT];
+    float m = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        F kf;
+        kf.load(zk + (32 * j + r) * G::LD, true, h);
+        f32x16 s = {};
+        s = F::mma(kf, qf, s);
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const float x = 32 * j + acc_row(t, lane) < seq ? s[t] * scale : -INFINITY;
+            s[t] = x;
+            m = fmaxf(m, x);
+        }
+        st[j] = s;
+    }
+    m = fmaxf(m, __shfl_xor(m, 32));  // key 0 is real: finite
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) {
+            const float e = 32 * j + acc_row(t, lane) < seq ? expf(st[j][t] - m) : 0.f;
+            st[j][t] = e;
+            sum += e;
+        }
+    sum += __shfl_xor(sum, 32);
+    const float inv = 1.f / sum;
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int t = 0; t < 16; ++t) st[j][t] *= inv;
+    if (rv && h == 0) lse[p * seq + row] = m + logf(sum);
+
+    // O^T[channel][query row] = sum_j v_j^T P_j^T, one chain over the key tiles
+#pragma unroll
+    for (int tile = 0; tile < G::TILES; ++tile) {
+        f32x16 o = {};
+#pragma unroll
+        for (int j = 0; j < NT; ++j)
+            o = acc_product<D, G::LD>(zv + 32 * j * G::LD, st[j], tile, r, h, o);
+        store_tile<T, D>(out + ro, rv, o, 1.f, tile, h);
+    }
+}
+
+template <typename T, int D, int NT>
+__global__ __launch_bounds__(NT* kWave) void attn_long_bwd_kernel(
+    const T* __restrict__ q, const T* __restrict__ k, const T* __restrict__ v,
+    const T* __restrict__ out, const float* __restrict__ lse, const T* __restrict__ dout,
+    T* __restrict__ dq, T* __restrict__ dk, T* __restrict__ dv, int seq, int heads, float scale) {
+    typedef LongGeo<T, D, NT> L;
+    typedef typename L::G G;
+    typedef typename G::F F;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    T* zq = (T*)smem;
+    T* zk = zq + L::IMG;
+    T* zv = zk + L::IMG;
+    T* zd = zv + L::IMG;
+    float* xd = (float*)(zd + L::IMG);  // D_i, i < 32 NT
+    float* xl = xd + L::ROWS;           // lse_i
+    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+    const int64_t p = blockIdx.x;
+    const int64_t b = p / heads;
+    const int hd = (int)(p - b * heads);
+    const int row = 32 * w + r;  // this lane's query and key, and the row it stages
+    const bool rv = row < seq;
+    const int64_t ro = ((b * seq + row) * heads + hd) * D;
+
+    // D of the wave's own rows: the diagonal of dO O^T from the chain that also
+    // makes dP = dO V^T (attn_bwd_kernel); 0 for a padded row
+    F dof, qf, kf, vf;
+    dof.load(dout + ro, rv, h);
+    float dl = 0.f;
+    {
+        F of;
+        of.load(out + ro, rv, h);
+        f32x16 e = {};
+        e = F::mma(dof, of, e);
+#pragma unroll
+        for (int t = 0; t < 16; ++t)
+            if (t == (r & 3) + 4 * (r >> 3)) dl = e[t];
+    }
+    dl = __shfl(dl, r + 32 * ((r >> 2) & 1));
+    const float ll = rv ? lse[p * seq + row] : 0.f;
+    qf.load(q + ro, rv, h);
+    kf.load(k + ro, rv, h);
+    vf.load(v + ro, rv, h);
+    qf.store_lds(zq + row * G::LD, h);
+    kf.store_lds(zk + row * G::LD, h);
+    vf.store_lds(zv + row * G::LD, h);
+    dof.store_lds(zd + row * G::LD, h);
+    if (h == 0) {
+        xd[row] = dl;
+        xl[row] = ll;
+    }
+    __syncthreads();
+
+    // owner of key tile w: key `row` on the lane, query 32 i + acc_row(t) in the
+    // registers (registers 4 g .. 4 g + 3 are the four queries 32 i + 8 g + 4 h + ..)
+    {
+        f32x16 dva[G::TILES], dka[G::TILES];
+#pragma unroll
+        for (int tile = 0; tile < G::TILES; ++tile) dva[tile] = dka[tile] = f32x16{};
+#pragma unroll
+        for (int i = 0; i < NT; ++i) {
+            F qi, di;
+            qi.load(zq + (32 * i + r) * G::LD, true, h);
+            di.load(zd + (32 * i + r) * G::LD, true, h);
+            f32x16 s = {}, dp = {};
+            s = F::mma(qi, kf, s);
+            dp = F::mma(di, vf, dp);
+            f32x16 pm, ds;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 l4 = *(const f32x4*)(xl + 32 * i + 8 * g + 4 * h);
+                const f32x4 d4 = *(const f32x4*)(xd + 32 * i + 8 * g + 4 * h);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int t = 4 * g + e;
+                    const float pp = (rv && 32 * i + acc_row(t, lane) < seq)
+                                         ? expf(s[t] * scale - l4[e]) : 0.f;
+                    pm[t] = pp;
+                    ds[t] = pp * (dp[t] - d4[e]);
+                }
+            }
+#pragma unroll
+            for (int tile = 0; tile < G::TILES; ++tile) {
+                // dV^T[c][key] += sum_i dO[i][c] P[i][key]; dK^T[c][key] += sum_i q[i][c] dS[i][key]
+                dva[tile] = acc_product<D, G::LD>(zd + 32 * i * G::LD, pm, tile, r, h, dva[tile]);
+                dka[tile] = acc_product<D, G::LD>(zq + 32 * i * G::LD, ds, tile, r, h, dka[tile]);
+            }
+        }
+#pragma unroll
+        for (int tile = 0; tile < G::TILES; ++tile) {
+            store_tile<T, D>(dv + ro, rv, dva[tile], 1.f, tile, h);
+            store_tile<T, D>(dk + ro, rv, dka[tile], scale, tile, h);
+        }
+    }
+
+    // owner of query tile w: query `row` on the lane, key 32 j + acc_row(t) in
+    // the registers; dQ^T[c][query] = scale sum_j k[j][c] dS^T[j][query]
+    {
+        f32x16 dqa[G::TILES];
+#pragma unroll
+        for (int tile = 0; tile < G::TILES; ++tile) dqa[tile] = f32x16{};
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+            F kj, vj;
+            kj.load(zk + (32 * j + r) * G::LD, true, h);
+            vj.load(zv + (32 * j + r) * G::LD, true, h);
+            f32x16 s = {}, dp = {};
+            s = F::mma(kj, qf, s);
+            dp = F::mma(vj, dof, dp);
+            f32x16 dst;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const float pp = (rv && 32 * j + acc_row(t, lane) < seq)
+                                     ? expf(s[t] * scale - ll) : 0.f;
+                dst[t] = pp * (dp[t] - dl);
+            }
+#pragma unroll
+            for (int tile = 0; tile < G::TILES; ++tile)
+                dqa[tile] = acc_product<D, G::LD>(zk + 32 * j * G::LD, dst, tile, r, h, dqa[tile]);
+        }
+#pragma unroll
+        for (int tile = 0; tile < G::TILES; ++tile)
+            store_tile<T, D>(dq + ro, rv, dqa[tile], scale, tile, h);
+    }
+}
+
 int check_shape(const char* what, int32_t dtype, int64_t batch, int32_t seq, int32_t heads,
-                int32_t head_dim, float scale, int64_t* nprob) {
+                int32_t head_dim, float scale, int64_t* nprob, int32_t seq_lo = 1,
+                int32_t seq_hi = 32, int per_wg = kAttnWaves) {
     ML_REQUIRE(dtype == MLEARN_DTYPE_F32 || dtype == MLEARN_DTYPE_BF16,
                "%s: dtype %d (MLEARN_DTYPE_F32 or MLEARN_DTYPE_BF16)", what, dtype);
-    ML_REQUIRE(seq >= 1 && seq <= 32, "%s: seq %d outside 1..32", what, seq);
+    ML_REQUIRE(seq >= seq_lo && seq <= seq_hi, "%s: seq %d outside %d..%d", what, seq, seq_lo,
+               seq_hi);
     ML_REQUIRE(head_dim == 16 || head_dim == 32 || head_dim == 64,
                "%s: head_dim %d (16, 32 or 64)", what, head_dim);
     ML_REQUIRE(heads >= 1 && heads <= 65536, "%s: heads %d outside 1..65536", what, heads);
     ML_REQUIRE(batch >= 1, "%s: batch %lld < 1", what, (long long)batch);
     ML_REQUIRE(isfinite(scale), "%s: scale is not finite", what);
-    // one wave per (batch, head); kAttnWaves per workgroup, grid.x < 2^31
-    ML_REQUIRE(batch <= (((int64_t)1 << 31) - 1) * kAttnWaves / heads,
+    // per_wg (batch, head) problems per workgroup, grid.x < 2^31
+    ML_REQUIRE(batch <= (((int64_t)1 << 31) - 1) * per_wg / heads,
                "%s: batch %lld x heads %d exceeds one launch", what, (long long)batch, heads);
     *nprob = batch * heads;
     return MLEARN_OK;
@@ -1025,10 +1272,103 @@ int launch_pooled_bwd(const void* q, const void* k, const void* v, const float* 
     return check_launch("attention_pooled_bwd");
 }
 
+// One workgroup of NT = ceil(seq / 32) waves per problem.  The LDS attribute is
+// set once per instantiation and device, kept out of graph capture.
+template <typename T, int D, int NT>
+int launch_long_fwd_nt(const void* q, const void* k, const void* v, int64_t nprob, int32_t seq,
+                       int32_t heads, float scale, void* out, float* lse, hipStream_t st) {
+    auto fn = attn_long_fwd_kernel<T, D, NT>;
+    constexpr int lds = LongGeo<T, D, NT>::FWD_LDS;
+    if (int rc = set_lds_attr((const void*)fn, lds, "attention_long_fwd")) return rc;
+    (void)hipGetLastError();  // check_launch reports this launch, not an earlier call's error
+    hipLaunchKernelGGL(fn, dim3((unsigned)nprob), dim3(NT * kWave), lds, st, (const T*)q,
+                       (const T*)k, (const T*)v, (T*)out, lse, seq, heads, scale);
+    return check_launch("attention_long_fwd");
+}
+
+template <typename T, int D, int NT>
+int launch_long_bwd_nt(const void* q, const void* k, const void* v, const void* out,
+                       const float* lse, const void* dout, int64_t nprob, int32_t seq,
+                       int32_t heads, float scale, void* dq, void* dk, void* dv, hipStream_t st) {
+    auto fn = attn_long_bwd_kernel<T, D, NT>;
+    constexpr int lds = LongGeo<T, D, NT>::BWD_LDS;
+    if (int rc = set_lds_attr((const void*)fn, lds, "attention_long_bwd")) return rc;
+    (void)hipGetLastError();  // check_launch reports this launch, not an earlier call's error
+    hipLaunchKernelGGL(fn, dim3((unsigned)nprob), dim3(NT * kWave), lds, st, (const T*)q,
+                       (const T*)k, (const T*)v, (const T*)out, lse, (const T*)dout, (T*)dq,
+                       (T*)dk, (T*)dv, seq, heads, scale);
+    return check_launch("attention_long_bwd");
+}
+
+// f<T, D, NT>(args...) for the runtime (head_dim, seq): NT 2, 3 or 4
+#define ML_ATTN_LONG_NT(f, DD, ...)                                  \
+    (seq <= 64 ? f<T, DD, 2>(__VA_ARGS__)                            \
+               : seq <= 96 ? f<T, DD, 3>(__VA_ARGS__) : f<T, DD, 4>(__VA_ARGS__))
+#define ML_ATTN_LONG(f, ...)                                         \
+    (head_dim == 16 ? ML_ATTN_LONG_NT(f, 16, __VA_ARGS__)            \
+                    : head_dim == 32 ? ML_ATTN_LONG_NT(f, 32, __VA_ARGS__) \
+                                     : ML_ATTN_LONG_NT(f, 64, __VA_ARGS__))
+
+template <typename T>
+int launch_long_fwd(const void* q, const void* k, const void* v, int64_t nprob, int32_t seq,
+                    int32_t heads, int32_t head_dim, float scale, void* out, float* lse,
+                    hipStream_t st) {
+    return ML_ATTN_LONG(launch_long_fwd_nt, q, k, v, nprob, seq, heads, scale, out, lse, st);
+}
+
+template <typename T>
+int launch_long_bwd(const void* q, const void* k, const void* v, const void* out, const float* lse,
+                    const void* dout, int64_t nprob, int32_t seq, int32_t heads, int32_t head_dim,
+                    float scale, void* dq, void* dk, void* dv, hipStream_t st) {
+    return ML_ATTN_LONG(launch_long_bwd_nt, q, k, v, out, lse, dout, nprob, seq, heads, scale, dq,
+                        dk, dv, st);
+}
+#undef ML_ATTN_LONG
+#undef ML_ATTN_LONG_NT
+
 }  // namespace
 }  // namespace ml
 
 extern "C" {
+
+int mlearn_attention_long_fwd(const void* q, const void* k, const void* v, int32_t dtype,
+                              int64_t batch, int32_t seq, int32_t heads, int32_t head_dim,
+                              float scale, void* out, float* lse, mlearn_stream_t stream) {
+    using namespace ml;
+    ML_REQUIRE(q && k && v && out && lse, "attention_long_fwd: null pointer");
+    int64_t nprob = 0;
+    if (int rc = check_shape("attention_long_fwd", dtype, batch, seq, heads, head_dim, scale,
+                             &nprob, 33, kLongMaxSeq, 1))
+        return rc;
+    ML_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out),
+               "attention_long_fwd: q, k, v, out must be 16-byte aligned");
+    if (dtype == MLEARN_DTYPE_BF16)
+        return launch_long_fwd<bf16>(q, k, v, nprob, seq, heads, head_dim, scale, out, lse,
+                                     S(stream));
+    return launch_long_fwd<float>(q, k, v, nprob, seq, heads, head_dim, scale, out, lse,
+                                  S(stream));
+}
+
+int mlearn_attention_long_bwd(const void* q, const void* k, const void* v, const void* out,
+                              const float* lse, const void* dout, int32_t dtype, int64_t batch,
+                              int32_t seq, int32_t heads, int32_t head_dim, float scale, void* dq,
+                              void* dk, void* dv, mlearn_stream_t stream) {
+    using namespace ml;
+    ML_REQUIRE(q && k && v && out && lse && dout && dq && dk && dv,
+               "attention_long_bwd: null pointer");
+    int64_t nprob = 0;
+    if (int rc = check_shape("attention_long_bwd", dtype, batch, seq, heads, head_dim, scale,
+                             &nprob, 33, kLongMaxSeq, 1))
+        return rc;
+    ML_REQUIRE(aligned16(q) && aligned16(k) && aligned16(v) && aligned16(out) && aligned16(dout) &&
+                   aligned16(dq) && aligned16(dk) && aligned16(dv),
+               "attention_long_bwd: q, k, v, out, dout, dq, dk, dv must be 16-byte aligned");
+    if (dtype == MLEARN_DTYPE_BF16)
+        return launch_long_bwd<bf16>(q, k, v, out, lse, dout, nprob, seq, heads, head_dim, scale,
+                                     dq, dk, dv, S(stream));
+    return launch_long_bwd<float>(q, k, v, out, lse, dout, nprob, seq, heads, head_dim, scale, dq,
+                                  dk, dv, S(stream));
+}
 
 int mlearn_attention_fwd(const void* q, const void* k, const void* v, int32_t dtype, int64_t batch,
                          int32_t seq, int32_t heads, int32_t head_dim, float scale, void* out,

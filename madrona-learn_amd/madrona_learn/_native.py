@@ -267,6 +267,10 @@ _SIGNATURES = {
                                        c_float, _P, _P, _S]),
     "mlearn_attention_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32, c_int32,
                                        c_int32, c_float, _P, _P, _P, _S]),
+    "mlearn_attention_long_fwd": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int32, c_int32,
+                                            c_int32, c_float, _P, _P, _S]),
+    "mlearn_attention_long_bwd": (c_int32, [_P, _P, _P, _P, _P, _P, c_int32, c_int64, c_int32,
+                                            c_int32, c_int32, c_float, _P, _P, _P, _S]),
     "mlearn_attention_pooled_fwd": (c_int32, [_P, _P, _P, c_int32, c_int64, c_int32, c_int32,
                                               c_int32, c_float, _P, _P, _S]),
     "mlearn_attention_pooled_bwd": (c_int32, [_P, _P, _P, _P, _P, c_int32, c_int64, c_int32,

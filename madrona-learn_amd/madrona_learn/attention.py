@@ -9,11 +9,17 @@ models.py:59-97):
   matmul), any device, dtype and shape;
 * ``attention_hip``: the gfx950 kernels mlearn_attention_fwd / _bwd
   (csrc/attention.hip) under torch autograd, one wave per (batch row, head);
-  f32 or bf16 on the GPU, seq <= 32, head_dim 16, 32 or 64.
+  f32 or bf16 on the GPU, seq <= 32, head_dim 16, 32 or 64;
+* ``attention_long_hip``: mlearn_attention_long_fwd / _bwd for seq 33..128,
+  one workgroup of ceil(seq / 32) waves per (batch row, head), otherwise the
+  same domain.
 
 ``attention(q, k, v, scale, kernel)`` picks one: kernel 0 = the library's
 choice (``_default_is_hip``, from the measured table in DESIGN.md), 1 = torch,
-2 = the HIP kernel (NotImplementedError where it does not apply).
+2 = the one-wave HIP kernel (NotImplementedError where it does not apply), 3 =
+HIP at every size a kernel serves: what 2 gives at seq <= 32, the long kernels
+at seq 33..128, NotImplementedError elsewhere.  The long kernels are opt-in:
+only 3 reaches them (0 keeps the composition above 32 entities).
 
 ``attention_pooled(q, k, v, scale, kernel)`` is the same attention followed
 by the mean over the query (entity) axis, ``[batch, heads, head_dim]``: all
@@ -21,6 +27,8 @@ that EntitySelfAttentionNet keeps of it.  ``attention_pooled_torch`` is the
 composition's mean; ``attention_pooled_hip`` runs mlearn_attention_pooled_fwd
 / _bwd, which fold the mean into the kernel (pbar = mean_q P, pooled = pbar V)
 and never form the [batch, seq, heads, head_dim] output or its gradient.
+Under kernel 3 at seq 33..128 it is ``attention_long_hip(...).mean(dim=1)``
+(there is no pooled long kernel).
 """
 
 import torch
@@ -28,6 +36,7 @@ import torch
 from . import _native as nat
 
 MAX_SEQ = 32
+MAX_SEQ_LONG = 128
 HEAD_DIMS = (16, 32, 64)
 
 
@@ -37,20 +46,25 @@ def attention_torch(q, k, v, scale):
     return torch.einsum("bhqk,bkhd->bqhd", p, v)
 
 
-def hip_problem(q):
+def hip_problem(q, lo=1, hi=MAX_SEQ):
     """Why the HIP kernel does not take q's attention problem (None: it does)."""
     if not q.is_cuda:
         return f"tensors on {q.device} (the kernel runs on the GPU)"
     if q.dtype not in (torch.float32, torch.bfloat16):
         return f"dtype {q.dtype} (float32 or bfloat16)"
     B, S, H, D = q.shape
-    if not 1 <= S <= MAX_SEQ:
-        return f"seq {S} outside 1..{MAX_SEQ}"
+    if not lo <= S <= hi:
+        return f"seq {S} outside {lo}..{hi}"
     if D not in HEAD_DIMS:
         return f"head_dim {D} (one of {HEAD_DIMS})"
     if B < 1 or H < 1:
         return "an empty batch"
     return None
+
+
+def hip_long_problem(q):
+    """hip_problem for the long kernels (seq 33..MAX_SEQ_LONG)."""
+    return hip_problem(q, MAX_SEQ + 1, MAX_SEQ_LONG)
 
 
 def _aligned(t):
@@ -61,19 +75,19 @@ def _aligned(t):
 class _Attention(torch.autograd.Function):
     """mlearn_attention_fwd with mlearn_attention_bwd as its gradient; q, k,
     v, out and the log-sum-exp rows are kept for the backward, which
-    recomputes the probabilities."""
+    recomputes the probabilities.  entry: "attention" or "attention_long"."""
 
     @staticmethod
-    def forward(ctx, q, k, v, scale):
+    def forward(ctx, q, k, v, scale, entry="attention"):
         q, k, v = _aligned(q), _aligned(k), _aligned(v)
         B, S, H, D = q.shape
         out = torch.empty_like(q)
         lse = torch.empty((B, H, S), dtype=torch.float32, device=q.device)
-        nat.check(nat.lib().mlearn_attention_fwd(
+        nat.check(getattr(nat.lib(), f"mlearn_{entry}_fwd")(
             nat.ptr(q), nat.ptr(k), nat.ptr(v), nat.dtype_code(q.dtype), B, S, H, D, float(scale),
-            nat.ptr(out), nat.ptr(lse), nat.stream_handle()), "attention_fwd")
+            nat.ptr(out), nat.ptr(lse), nat.stream_handle()), f"{entry}_fwd")
         ctx.save_for_backward(q, k, v, out, lse)
-        ctx.scale = float(scale)
+        ctx.scale, ctx.entry = float(scale), entry
         return out
 
     @staticmethod
@@ -82,11 +96,11 @@ class _Attention(torch.autograd.Function):
         B, S, H, D = q.shape
         dout = _aligned(dout.to(q.dtype))
         dq, dk, dv = torch.empty_like(q), torch.empty_like(q), torch.empty_like(q)
-        nat.check(nat.lib().mlearn_attention_bwd(
+        nat.check(getattr(nat.lib(), f"mlearn_{ctx.entry}_bwd")(
             nat.ptr(q), nat.ptr(k), nat.ptr(v), nat.ptr(out), nat.ptr(lse), nat.ptr(dout),
             nat.dtype_code(q.dtype), B, S, H, D, ctx.scale, nat.ptr(dq), nat.ptr(dk), nat.ptr(dv),
-            nat.stream_handle()), "attention_bwd")
-        return dq, dk, dv, None
+            nat.stream_handle()), f"{ctx.entry}_bwd")
+        return dq, dk, dv, None, None
 
 
 def attention_hip(q, k, v, scale):
@@ -96,6 +110,18 @@ def attention_hip(q, k, v, scale):
     if k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
         raise ValueError("attention: q, k and v must share one shape and dtype")
     return _Attention.apply(q, k, v, scale)
+
+
+def attention_long_hip(q, k, v, scale):
+    why = hip_long_problem(q)
+    if why is not None:
+        raise NotImplementedError(f"the long HIP attention kernel does not take {why}")
+    if k.shape != q.shape or v.shape != q.shape or k.dtype != q.dtype or v.dtype != q.dtype:
+        raise ValueError("attention: q, k and v must share one shape and dtype")
+    return _Attention.apply(q, k, v, scale, "attention_long")
+
+
+_KERNELS = "0 (library's choice), 1 (torch), 2 (HIP, seq <= 32) or 3 (HIP, seq <= 128)"
 
 
 def _default_is_hip(dtype, seq):
@@ -108,12 +134,14 @@ def _default_is_hip(dtype, seq):
 
 
 def attention(q, k, v, scale, kernel=0):
-    if kernel == 2:
+    if kernel == 3 and q.shape[1] > MAX_SEQ:
+        return attention_long_hip(q, k, v, scale)
+    if kernel in (2, 3):
         return attention_hip(q, k, v, scale)
     if kernel == 1:
         return attention_torch(q, k, v, scale)
     if kernel != 0:
-        raise ValueError(f"attention_kernel {kernel}: 0 (library's choice), 1 (torch) or 2 (HIP)")
+        raise ValueError(f"attention_kernel {kernel}: {_KERNELS}")
     if hip_problem(q) is None and _default_is_hip(q.dtype, q.shape[1]):
         return attention_hip(q, k, v, scale)
     return attention_torch(q, k, v, scale)
@@ -172,12 +200,14 @@ def _default_pooled_is_hip(dtype, seq):
 
 
 def attention_pooled(q, k, v, scale, kernel=0):
-    if kernel == 2:
+    if kernel == 3 and q.shape[1] > MAX_SEQ:
+        return attention_long_hip(q, k, v, scale).mean(dim=1)
+    if kernel in (2, 3):
         return attention_pooled_hip(q, k, v, scale)
     if kernel == 1:
         return attention_pooled_torch(q, k, v, scale)
     if kernel != 0:
-        raise ValueError(f"attention_kernel {kernel}: 0 (library's choice), 1 (torch) or 2 (HIP)")
+        raise ValueError(f"attention_kernel {kernel}: {_KERNELS}")
     if hip_problem(q) is None and _default_pooled_is_hip(q.dtype, q.shape[1]):
         return attention_pooled_hip(q, k, v, scale)
     return attention_pooled_torch(q, k, v, scale)

@@ -194,7 +194,11 @@ class SelfAttention(nn.Module):  # models.py:59-97 (flax nn.SelfAttention)
     attention_kernel (class attribute, as PPO.step_kernel): 0 = the library's
     choice, 1 = the torch composition (matmul, softmax in f32, matmul), 2 =
     the HIP kernel (NotImplementedError where it does not apply: CPU tensors,
-    fp16, more than 32 entities, a head_dim other than 16 / 32 / 64)."""
+    fp16, more than 32 entities, a head_dim other than 16 / 32 / 64), 3 = HIP
+    at every size a kernel serves: exactly what 2 gives up to 32 entities, the
+    long kernels (one workgroup per problem, attention.attention_long_hip) at
+    33..128 entities, NotImplementedError elsewhere.  The long kernels are
+    opt-in: 0 keeps the composition above 32 entities."""
 
     attention_kernel = 0
 
