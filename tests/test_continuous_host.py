@@ -155,39 +155,44 @@ def test_bad_arguments_are_rejected_without_gpu():
     nat = _nat()
     L = nat.lib()
     buf = np.zeros(64, np.float32)
-    p = buf.ctypes.data_as(ctypes.c_void_p)  # (never read: every call is refused first)
+    # host memory, never read: every call made below is refused by the
+    # argument checks, which run before anything is launched
+    p = buf.ctypes.data_as(ctypes.c_void_p)
     F32 = nat.DTYPE_F32
 
     def calls(lay, ld=8, dtype=F32, means=p, out=p, ld_d=8):
+        """The four entry points on these arguments, as callables: a caller
+        makes only the calls its arguments invalidate."""
         return [
-            L.mlearn_continuous_sample(means, ld, p, ld, dtype, lay, 2, 1, 2, None, 0, 0, 1, out,
-                                       None, None),
-            L.mlearn_continuous_sample_host(means, ld, p, ld, dtype, lay, 2, 1, 2, None, 0, 0, 1,
-                                            out, None),
-            L.mlearn_continuous_stats(means, ld, p, ld, dtype, lay, 2, p, out, p, None),
-            L.mlearn_continuous_stats_bwd(means, ld, p, ld, dtype, lay, 2, p, None, None, out,
-                                          ld_d, p, ld_d, None),
+            lambda: L.mlearn_continuous_sample(means, ld, p, ld, dtype, lay, 2, 1, 2, None, 0, 0,
+                                               1, out, None, None),
+            lambda: L.mlearn_continuous_sample_host(means, ld, p, ld, dtype, lay, 2, 1, 2, None,
+                                                    0, 0, 1, out, None),
+            lambda: L.mlearn_continuous_stats(means, ld, p, ld, dtype, lay, 2, p, out, p, None),
+            lambda: L.mlearn_continuous_stats_bwd(means, ld, p, ld, dtype, lay, 2, p, None, None,
+                                                  out, ld_d, p, ld_d, None),
         ]
 
     good = cref.layout(nat, [(0.1, 1.0), (0.2, 0.2)], 4)
-    for rc in calls(good, means=None):
-        _einval(rc, "null")
-    for rc in calls(good, out=None):
-        _einval(rc, "null")
-    for rc in calls(good, ld=7):
-        _einval(rc, "stride")
-    _einval(calls(good, ld_d=7)[3], "stride")
-    for rc in calls(good, dtype=2):
-        _einval(rc, "dtype")
+    for call in calls(good, means=None):
+        _einval(call(), "null")
+    for call in calls(good, out=None):
+        _einval(call(), "null")
+    for call in calls(good, ld=7):
+        _einval(call(), "stride")
+    # ld_d is the backward's alone: the other three calls would be valid
+    _einval(calls(good, ld_d=7)[3](), "stride")
+    for call in calls(good, dtype=2):
+        _einval(call(), "dtype")
     for G, D, word in ((0, 4, "num_groups"), (nat.MAX_GROUPS + 1, 1, "num_groups"),
                        (2, 0, "num_dims"), (16, 65, "1024")):
         lay = cref.layout(nat, [(0.1, 1.0)] * min(max(G, 0), nat.MAX_GROUPS), 1)
         lay.num_groups, lay.num_dims = G, D
-        for rc in calls(lay, ld=2048, ld_d=2048):
-            _einval(rc, word)
+        for call in calls(lay, ld=2048, ld_d=2048):
+            _einval(call(), word)
     for bad in ((0.0, 1.0), (-0.1, 1.0), (0.5, 0.4), (float("nan"), 1.0)):
-        for rc in calls(cref.layout(nat, [(0.1, 1.0), bad], 4)):
-            _einval(rc, "group 1")
+        for call in calls(cref.layout(nat, [(0.1, 1.0), bad], 4)):
+            _einval(call(), "group 1")
     with pytest.raises(ValueError):
         nat.continuous_layout(_cfgs()[:1] + [type(_cfgs()[0])(0.1, 1.0, 2)])
 

@@ -11,7 +11,11 @@ as a matrix-core operand, each output once; pbar stays f32).
 The measured ratios go to MLEARN_TEST_REPORT_DIR/attention_pooled_<dtype>_<shape>.json.
 Largest ratios measured on MI355X: f32 1.41 (lse at 5x31x1x64; 1.36 on dv at
 2x17x2x32; bound 4), bf16 0.108 (dv at 2x17x2x32; bound 1; pooled equals
-pooled_ref bit for bit at every shape).  The module test: 2.03 on the key
+pooled_ref bit for bit at every shape).
+Largest ratios measured on MI355X at 3x9x2x64 and 2x24x3x16: f32 1.27 (lse at
+3x9x2x64; pooled 1.22, dv 1.07, dk 1.00, dq 0.92), bf16 0.032 (dk at 2x24x3x16;
+dq 0.003; pooled and dv equal pooled_ref bit for bit).
+The module test: 2.03 on the key
 bias' gradient (analytically zero, rounding noise in every evaluation), 1.08 or
 less on the other tensors.
 """

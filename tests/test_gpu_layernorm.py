@@ -23,6 +23,10 @@ MLEARN_TEST_REPORT_DIR/layernorm_<dtype>_<act>_<shape>.json.
 Largest ratios measured on MI355X: f32 form (bound 4) 2.20 (mean at 2x1024
 under bf16 inputs), 2.07 (dscale at 2x256, f32), 1.61 (y), 1.20 (dbias), 1.13
 (dx), 1.00 (rstd); bf16 form (bound 1) 0.0077 (y at 1025x64), 0.00015 (dx).
+Largest ratios measured on MI355X at the widths 129 to 513 (every tier in
+both forms): f32 form 2.07 (mean at 2x300, f32), 1.54 (y at 2x300), 1.52
+(dscale at 2x300), 1.01 (dx), 1.00 (rstd, dbias); bf16 form: y and dx equal the
+bf16-mode restatement bit for bit at all six shapes.
 The module tests: 2.91 on the key bias' gradient of the entity trunk, which is
 analytically zero (softmax is shift-invariant) and rounding noise in every
 evaluation, 1.31 or less on every other tensor; MLP 1.10 or less.
@@ -41,7 +45,9 @@ from tests.test_gpu_entity_attention import _entity_training, _named, f32_bound_
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1), (3, 5), (5, 33), (4, 64), (7, 128), (2, 256), (3, 1000), (2, 1024), (130, 64)]
+SHAPES = [(1, 1), (3, 5), (5, 33), (4, 64), (7, 128), (2, 256), (3, 1000), (2, 1024), (130, 64),
+          # every width tier in both forms (tests/test_dispatch_coverage_host.py)
+          (3, 129), (3, 257), (2, 300), (5, 384), (2, 512), (3, 513)]
 LARGE = [(2051, 96), (1025, 64)]
 TENSORS = ("y", "mean", "rstd", "dx", "dscale", "dbias")
 ACT_CODE = {None: 0, "relu": 1, "leaky_relu": 2}
@@ -199,12 +205,13 @@ def test_kernel_matches_restatement_many_workgroups(gpu, shape, dtype):
 
 @pytest.mark.parametrize("act", [None, "leaky_relu"], ids=lambda a: ACT_TAG[a])
 @pytest.mark.parametrize("dtype", ["f32", "bf16"])
-@pytest.mark.parametrize("F", [33, 64])
+@pytest.mark.parametrize("F", [33, 64, 160, 384, 520])
 def test_column_slices_give_the_contiguous_bits(gpu, F, dtype, act):
     """x, dy, y, dx as the slices [:, 3:3 + F] of wider tensors (a base that is
     not 16-byte aligned: the element-wise form) against the contiguous call
-    (F = 64: the 16-byte form): the same bits in all six outputs, every column
-    outside the slices untouched."""
+    (every F but 33: the 16-byte form): the same bits in all six outputs, every
+    column outside the slices untouched.  F = 160, 384, 520: the element-wise
+    form of the second, third and fourth width tier."""
     rows = 70
     c = case(rows, F, dtype, act is not None)
     _, a, _ = run_kernel(gpu, c, DT[dtype], act)
